@@ -11,14 +11,22 @@ single-GPU configs.  One step = one full-array core.Array.read (M/core/Array.jav
 of all 32 shards / 786,432 in-bounds inner chunks: index CRC + index parse + byte swap
 (+ transpose) + scatter, inputs already resident in HBM.  Synthetic data v(g) =
 lo32(splitmix64(g ^ 0x5A5A2026)) is written on the device and encoded by the product's own
-write path (zh_array_write); after warmup the decoded array is verified element-by-element
-on the device against the generator.
+write path (zh_array_write).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2|...]
+                  [--dump-outputs DIR] [--full]
 
 N=1 prints the headline line (weak scaling of one full array per GPU, which at N=1 is the
-single-GPU number), plus `extra_configs` (c3, c2 and c4 little-endian timed in the same
-process), a one-shot `zh_array_read` time and the CPU baseline.
+single-GPU number).  A plain run does what that figure needs and no more: encode, plan, W
+warmup steps, exactly K timed steps on one output allocation, the line.  --dump-outputs DIR
+then writes a fixed sample of what the last timed step decoded (dump_outputs below).
+
+--full adds everything else, in the same process: three fresh output allocations instead of
+one (value = the median one), on each the copy ceiling and store probe of its buffers and an
+element-by-element verify of the decoded array on the device against the generator;
+`gpu_state`; `extra_configs` (c3, c2, c4 little-endian and c4 with shuffled chunks, each
+verified), a one-shot `zh_array_read`, the 64³ small read, the host-inclusive and
+store-inclusive reads and the CPU baseline.
 
 N>1 (BASELINE.json configs[4]): ONE full array partitioned across the GPUs in
 contiguous y-slabs (512 rows at N=8, aligned to inner chunks), strong scaling.  Each rank
@@ -1375,6 +1383,28 @@ def small_read(dev, A, meta, sources, coords, shape, reps=200):
     return res
 
 
+def dump_outputs(dev, out, nel, path, nseg=1024, seg=4096):
+    """--dump-outputs: what the last timed step left in the output buffer, the C-order decoded
+    array a caller of the plan receives, as `path`/decoded_sample.npy.  The full array is 96 GiB,
+    so the file holds a fixed sample: `nseg` runs of `seg` consecutive elements (32 MiB as
+    float64, which holds a uint32 exactly), the first and the last run of the array and
+    nseg - 2 runs at offsets drawn once from a generator seeded with SEED — the same rows
+    [run, element] for every run with the same arguments, as the inputs are the same.  An array
+    no larger than the sample is written whole."""
+    import numpy as np
+    if nel <= nseg * seg:
+        got = np.frombuffer(dev.d2h(out, 4 * nel), np.uint32).reshape(1, nel)
+    else:
+        rng = np.random.default_rng(SEED)
+        starts = rng.integers(1, nel // seg - 1, nseg - 2) * seg
+        starts = np.sort(np.concatenate(([0, nel - seg], starts)))
+        got = np.stack([np.frombuffer(dev.d2h(out + 4 * int(s), 4 * seg), np.uint32)
+                        for s in starts])
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "decoded_sample.npy"), got.astype(np.float64))
+    return {"file": "decoded_sample.npy", "shape": list(got.shape), "dtype": "float64"}
+
+
 # ------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -1382,9 +1412,16 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1 read: beside the headline, everything else this benchmark "
+                         "measures and checks (see the module text); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1 read: after the timed steps write a fixed sample of the decoded "
+                         "array of the last step to DIR/decoded_sample.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N=1: skip extra_configs (c3, c2, c4le) and the one-shot read")
+                    help="--full: skip extra_configs (c3, c2, c4le) and the one-shot read")
     ap.add_argument("--op", default="read", choices=["read", "write"],
                     help="read: the decode path (the metric); write: zh_array_write, the "
                          "encode path (SURVEY §8(f) rank 1)")
@@ -1392,9 +1429,10 @@ def main():
                     help="--op write: elide 1/128 of the inner chunks (all fill_value), so the "
                          "write takes its second pass")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    ap.add_argument("--allocations", type=int, default=3,
+    ap.add_argument("--allocations", type=int, default=None,
                     help="N=1 read: time the K steps on this many fresh output allocations "
-                         "(value = the median one; min and max alongside)")
+                         "(value = the median one; min and max alongside); default 1, with "
+                         "--full 3")
     ap.add_argument("--mode", default=None, choices=["weak", "strong"],
                     help="default: weak at N=1 (one full array), strong at N>1 (one array "
                          "split into per-GPU slabs + gather + host-terminated copy)")
@@ -1411,6 +1449,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="N>1 harness without a GPU (launch, partition, barrier, JSON line)")
     args = ap.parse_args()
+    if args.allocations is None:
+        args.allocations = 3 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -1418,6 +1458,8 @@ def main():
     if args.gpus != ws:
         log(f"warning: --gpus {args.gpus} but WORLD_SIZE {ws}: measuring {ws} rank(s)")
     mode = args.mode or ("strong" if ws > 1 else "weak")
+    if args.dump_outputs and (ws > 1 or mode == "strong" or args.op != "read" or args.dry_run):
+        ap.error("--dump-outputs covers the single-GPU read (--gpus 1, --op read)")
     if args.gather_backend == "none":
         args.gather_backend = None
     dist = Dist(ws, need_torch=mode == "strong")
@@ -1502,22 +1544,25 @@ def main():
     sources = [(shard_slab + o, s) for o, s in zip(offs, sizes)]
     plan = dev.plan(meta, sources, [0] * n, shape, flags)
     st = plan.stats()
-    state0 = gpu_state(dev.device, static=True) if rank == 0 else None
-    # the headline over several fresh output allocations (which physical
-    # memory a 96 GiB buffer gets moves the rate; DESIGN §4 "Placement"): W warmup steps, the
-    # verify, then exactly K timed steps on each; value = the median allocation's rate
+    full = args.full
+    state0 = gpu_state(dev.device, static=True) if full and rank == 0 else None
+    # the headline: W warmup steps, then exactly K timed steps.  --full: over several fresh
+    # output allocations (which physical memory a 96 GiB buffer gets moves
+    # the rate; DESIGN §4 "Placement"), each with its copy ceiling before and the verify after
+    # the warmup; value = the median allocation's rate
     runs = []
     for a in range(max(1, args.allocations)):
         if a:
             out = reallocate(dev, out, max(out_bytes, tot), a)
-        ev = ceiling_probe(dev, out, shard_slab, out_bytes)
+        ev = ceiling_probe(dev, out, shard_slab, out_bytes) if full else {}
         dev.memset(out, 0, out_bytes)
         for _ in range(max(1, args.warmup)):
             plan.execute(out)
         plan.wait()
-        bad = dev.synth_verify(out, shape, [0] * n, shape, 4, SEED)
-        if bad:
-            raise SystemExit(f"decode verification FAILED: {bad} mismatching elements")
+        if full:
+            bad = dev.synth_verify(out, shape, [0] * n, shape, 4, SEED)
+            if bad:
+                raise SystemExit(f"decode verification FAILED: {bad} mismatching elements")
         plan.set_timing(True)
         dist.barrier()
         dev.sync()
@@ -1530,11 +1575,16 @@ def main():
         elapsed = dist.max(t_end - t_start)
         roof = roofline_of(plan, st, args.config if args.ydiv == 1 else None)
         plan.set_timing(False)
-        ev["frac_of_copy_ceiling"] = round(roof["achieved"] / ev["copy_ceiling_GBps"], 4)
+        if full:
+            ev["frac_of_copy_ceiling"] = round(roof["achieved"] / ev["copy_ceiling_GBps"], 4)
         runs.append({"elapsed": elapsed, "roofline": roof, "evidence": ev,
-                     "verified_elements": nel})
+                     "verified_elements": nel if full else 0})
         log(f"[rank {rank}] allocation {a}: {args.steps * out_bytes / elapsed / GiB:.1f} GiB/s, "
-            f"kernel {roof['kernel_ms']} ms, {json.dumps(ev)} (verified {nel} elements)")
+            f"kernel {roof['kernel_ms']} ms, {json.dumps(ev)} "
+            f"(verified {nel if full else 0} elements)")
+    dumped = None
+    if args.dump_outputs:  # the last timed step's output, before anything else writes to it
+        dumped = dump_outputs(dev, out, nel, args.dump_outputs)
     order = sorted(range(len(runs)), key=lambda i: runs[i]["elapsed"])
     med = runs[order[len(runs) // 2]]  # the median (of an even count, the slower middle one)
     elapsed = med["elapsed"]
@@ -1546,18 +1596,18 @@ def main():
               "GiBps": [round(ws * args.steps * out_bytes / r["elapsed"] / GiB, 2)
                         for r in runs],
               "kernel_ms": [r["roofline"]["kernel_ms"] for r in runs],
-              "frac": [r["roofline"]["frac"] for r in runs],
-              "copy_ceiling_GBps": [r["evidence"]["copy_ceiling_GBps"] for r in runs],
-              "store_probe_GBps": [r["evidence"]["store_probe_GBps"] for r in runs],
-              "frac_of_copy_ceiling": [r["evidence"]["frac_of_copy_ceiling"] for r in runs]}
+              "frac": [r["roofline"]["frac"] for r in runs]}
+    if full:
+        for k in ("copy_ceiling_GBps", "store_probe_GBps", "frac_of_copy_ceiling"):
+            allocs[k] = [r["evidence"][k] for r in runs]
     allocs["GiBps_min"], allocs["GiBps_max"] = min(allocs["GiBps"]), max(allocs["GiBps"])
     hinc = None
-    if (not args.no_host_inclusive and ws == 1 and args.ydiv == 1 and args.config == "c4"
-            and meta.chain.sharded):
+    if (full and not args.no_host_inclusive and ws == 1 and args.ydiv == 1
+            and args.config == "c4" and meta.chain.sharded):
         hinc = host_inclusive(dev, A, meta, coords, offs, sizes, shard_slab, out)
         log(f"[rank {rank}] host-inclusive: {hinc}")
     cpu = None
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline and meta.chain.sharded:
+    if full and rank == 0 and ws == 1 and not args.no_cpu_baseline and meta.chain.sharded:
         cpu = cpu_baseline(dev, A, L, meta, shard_slab + offs[0], sizes[0], args.cpu_budget)
         log(f"[rank {rank}] cpu baseline: {json.dumps(cpu)}")
 
@@ -1575,12 +1625,17 @@ def main():
                    "output_allocation": f"{alloc_kind} (the output and the shard slab)"},
         "roofline": roofline,
         "allocations": allocs,
-        "gpu_state": {"start": state0, "end": gpu_state(dev.device) if rank == 0 else None},
+        "full": full,
         "cpu_baseline": cpu,
     }
+    if full:
+        line["gpu_state"] = {"start": state0,
+                             "end": gpu_state(dev.device) if rank == 0 else None}
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     if hinc is not None:
         line["host_inclusive"] = hinc
-    if not args.no_extras and ws == 1 and args.ydiv == 1 and args.config == "c4":
+    if full and not args.no_extras and ws == 1 and args.ydiv == 1 and args.config == "c4":
         line["oneshot_read"] = oneshot_read(dev, A, meta, sources, shape, out)
         line["small_read"] = small_read(dev, A, meta, sources, coords, shape)
         log(f"[rank {rank}] small read: {json.dumps(line['small_read'])}")

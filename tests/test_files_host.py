@@ -178,7 +178,7 @@ def test_shard_unreadable_index_is_store_exception(tmp_path):
     shape = [8, 16, 24]
     meta = A.make_meta(shape, [8, 16, 24], 4, sharded=True, inner_chunk_shape=[4, 8, 8])
     s = encode_oracle(meta, rand_array(shape, 4, seed=13))[0]
-    d = tmp_path / "store" / "c" / "0"
+    d = tmp_path / "store" / "c" / "0" / "0"  # chunk (0, 0, 0)'s key is c/0/0/0
     d.mkdir(parents=True)
     p = d / "0"
     p.write_bytes(s)
