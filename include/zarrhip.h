@@ -586,6 +586,50 @@ int zh_device_info(zh_ctx* ctx, char* name, size_t namelen, int64_t* total_mem,
 int zh_blosc_decompress(const void* src, size_t srclen, void* dst, size_t dstcap,
                         size_t* nbytes_out, char* err, size_t errlen);
 
+/* ---- blosc1 frames decoded on the device, a batch at a time ---------------------------
+ * Frames whose streams are LZ4, BloscLZ or stored raw are independent blocks of independent
+ * streams: the compressed bytes cross PCIe and one kernel decodes every stream of the batch
+ * (one workgroup per block, one wavefront per stream) and undoes the byte / bit shuffle.
+ * Memcpyed frames are one copy; zlib and zstd payloads are decoded by zh_blosc_decompress on
+ * the host and copied.  The decoded frames lie in one device buffer at dst_off. */
+typedef struct zh_blosc_frame {
+  const void* src;   /* the stored frame, host memory                               */
+  int64_t srclen;
+  int64_t dst_off;   /* out (plan): offset in the batch destination, 256-B aligned  */
+  int64_t nbytes;    /* out (plan): decoded size                                    */
+  int32_t where;     /* out (plan): 0 device streams, 1 host fallback (zlib / zstd
+                        payload: zh_blosc_decompress into pinned staging, then H2D),
+                        2 memcpyed                                                  */
+  int32_t status;    /* out: ZH_OK or this frame's error                            */
+} zh_blosc_frame;
+
+/* No device needed: validates headers with the checks and texts of zh_blosc_decompress's
+ * size query, fills dst_off / nbytes / where, returns the destination bytes or -zh_status
+ * (the first bad frame in batch order; its status field is set). */
+int64_t zh_blosc_batch_plan(zh_blosc_frame* frames, int64_t n, char* err, size_t errlen);
+
+/* Plans as above, stages the compressed bytes H2D through the context's pinned ring, decodes
+ * on `stream` (NULL: the context's), waits, and reports the first failing frame in batch order
+ * with the host decoder's text ("corrupt blosc block", ...) and status.  dst is device memory
+ * of dstcap >= the plan's bytes.  After a failed call dst is undefined; the context stays
+ * usable. */
+int zh_blosc_decode_batch(zh_ctx* ctx, zh_blosc_frame* frames, int64_t n, void* dst,
+                          int64_t dstcap, void* stream, char* err, size_t errlen);
+
+/* Diagnostic: milliseconds the decode kernel of the last successful zh_blosc_decode_batch in
+ * this process took, by device events around its launch (-1: none yet, or no device frame). */
+double zh_debug_blosc_kernel_ms(void);
+
+/* Diagnostic, no device: the block / stream table of one device-decoded frame, as rows of 6
+ * int64 — per block (0, offset in the decoded frame, size, typesize, shuffle kind: 0 none,
+ * 1 byte, 2 bit with the format-2 leftover rule, 3 bit with the format-3 rule, streams)
+ * followed by its streams (1, payload offset in the frame, csize, offset in the shuffled
+ * block, raw size, method: 0 raw copy, 1 LZ4, 2 BloscLZ).  Writes up to `cap` rows to `rows`
+ * (may be NULL) and returns their number, or -zh_status with err set (header and chain errors
+ * as zh_blosc_decompress words them; ZH_EUNSUPPORTED for memcpyed and host-decoded frames). */
+int64_t zh_debug_blosc_streams(const void* src, size_t srclen, int64_t* rows, int64_t cap,
+                               char* err, size_t errlen);
+
 /* ---- host byte-to-byte stage: zstd frames (RFC 8878) ------------------------------
  * Replaces zstd-jni inside ZstdCodec.decode (M/core/codec/core/ZstdCodec.java:14-22) and the
  * zstd compressor of blosc frames (BloscCodec.java; CodecBuilder.withBlosc() defaults to

@@ -86,6 +86,12 @@ class zh_shard_src(C.Structure):
                 ("npieces", C.c_int64)]
 
 
+class zh_blosc_frame(C.Structure):
+    """One blosc1 frame of a batched device decode (zarrhip.h zh_blosc_frame)."""
+    _fields_ = [("src", C.c_void_p), ("srclen", C.c_int64), ("dst_off", C.c_int64),
+                ("nbytes", C.c_int64), ("where", C.c_int32), ("status", C.c_int32)]
+
+
 class zh_file_store(C.Structure):
     """A FilesystemStore as the file reads name it (zarrhip.h zh_file_store)."""
     _fields_ = [("root", C.c_char_p), ("name", C.c_char_p)]

@@ -93,6 +93,10 @@ _SIGS = {
     "zh_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "zh_plan_staged_bytes": (C.c_int64, [P]),
     "zh_blosc_decompress": (C.c_int, [P, SZ, P, SZ, C.POINTER(SZ), C.c_char_p, SZ]),
+    "zh_blosc_batch_plan": (I64, [C.POINTER(A.zh_blosc_frame), I64, CH, SZ]),
+    "zh_blosc_decode_batch": (C.c_int, [P, C.POINTER(A.zh_blosc_frame), I64, P, I64, P, CH, SZ]),
+    "zh_debug_blosc_kernel_ms": (C.c_double, []),
+    "zh_debug_blosc_streams": (I64, [P, SZ, PI64, I64, CH, SZ]),
     "zh_zstd_decompress": (C.c_int, [P, SZ, P, SZ, C.POINTER(SZ), C.c_char_p, SZ]),
     "zh_zstd_compress_raw": (C.c_int, [P, SZ, C.c_int, P, SZ, C.POINTER(SZ)]),
     "zh_xxh64": (U64, [P, SZ, U64]),
@@ -412,6 +416,26 @@ class DeviceContext:
         check(st, err)
         return [int(sizes[i]) for i in range(n)]
 
+    def blosc_decode_batch(self, frames, stream=None):
+        """zh_blosc_batch_plan + zh_blosc_decode_batch over blosc1 frames (bytes-like, or
+        (address, nbytes) pairs of host memory the caller keeps alive): returns the device
+        buffer holding every decoded frame and, per frame, (dst_off, nbytes, where).  The
+        caller frees the buffer (self.free)."""
+        arr, keep = blosc_frame_array(frames)
+        err = C.create_string_buffer(1024)
+        total = self.L.zh_blosc_batch_plan(arr, len(frames), err, 1024)
+        if total < 0:
+            check(int(-total), err)
+        ptr = self.malloc(max(256, total), A.ZH_MALLOC_PLAIN)
+        try:
+            check(self.L.zh_blosc_decode_batch(self.h, arr, len(frames), P(ptr), max(256, total),
+                                               P(stream), err, 1024), err)
+        except BaseException:
+            self.free(ptr)
+            raise
+        del keep
+        return ptr, [(arr[i].dst_off, arr[i].nbytes, arr[i].where) for i in range(len(frames))]
+
     def host_staging(self, nbytes):
         """zh_host_staging: the context's page-locked staging (valid until the next call)."""
         p = P()
@@ -539,6 +563,45 @@ def array_read_pieces_multi(ctxs, meta, shards, offset, shape, out, flags, root=
     del keep
     check(st, err)
     return list(routes)
+
+
+def blosc_frame_array(frames):
+    """ctypes zh_blosc_frame[] for bytes-like frames or (address, nbytes) pairs; returns
+    (array, keepalive)."""
+    arr = (A.zh_blosc_frame * max(1, len(frames)))()
+    keep = []
+    for i, f in enumerate(frames):
+        if isinstance(f, tuple):
+            arr[i].src, arr[i].srclen = f[0], int(f[1])
+            continue
+        b = (C.c_char * max(1, len(f))).from_buffer_copy(bytes(f) or b"\0")
+        keep.append(b)
+        arr[i].src, arr[i].srclen = C.addressof(b), len(f)
+    return arr, keep
+
+
+def blosc_batch_plan(frames):
+    """zh_blosc_batch_plan (no device): (destination bytes, [(dst_off, nbytes, where)])."""
+    arr, keep = blosc_frame_array(frames)
+    err = C.create_string_buffer(1024)
+    total = lib().zh_blosc_batch_plan(arr, len(frames), err, 1024)
+    if total < 0:
+        check(int(-total), err)
+    return int(total), [(arr[i].dst_off, arr[i].nbytes, arr[i].where)
+                        for i in range(len(frames))]
+
+
+def blosc_streams(frame):
+    """zh_debug_blosc_streams (no device): the block / stream rows of one frame, 6 ints each."""
+    L = lib()
+    b = (C.c_char * max(1, len(frame))).from_buffer_copy(bytes(frame) or b"\0")
+    err = C.create_string_buffer(1024)
+    n = L.zh_debug_blosc_streams(b, len(frame), None, 0, err, 1024)
+    if n < 0:
+        check(int(-n), err)
+    rows = (C.c_int64 * max(1, 6 * n))()
+    L.zh_debug_blosc_streams(b, len(frame), rows, n, err, 1024)
+    return [tuple(rows[6 * k:6 * k + 6]) for k in range(n)]
 
 
 def path_array(paths):

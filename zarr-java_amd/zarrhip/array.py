@@ -9,7 +9,9 @@ chunk codec work done by the HIP path through the C-ABI (libzarrhip.so).
   access()                   M/core/Array.java:483-536   (ArrayAccessor)
 
 Byte-to-byte compressors stay on the host (north star): their frames are decoded here and
-the raw chunk bytes are handed to the device.
+the raw chunk bytes are handed to the device — except blosc frames, which
+one batched call decodes on the device when blosc is the chain's only host stage
+(ZH_BLOSC_DEVICE, zh_blosc_decode_batch).
 """
 import atexit
 import ctypes as C
@@ -23,12 +25,34 @@ import numpy as np
 
 from . import _abi as A
 from . import _lib
-from .codecs import device_chain, host_bb_decode, host_bb_encode
-from .errors import ZarrException, raise_for
+from .codecs import BloscCodec, device_chain, host_bb_decode, host_bb_encode
+from .errors import UnsupportedChainError, ZarrException, raise_for
 from .metadata import ZARR_JSON, ArrayMetadata
 
 _ctx = None
 _ctx_lock = threading.Lock()
+
+# ZH_BLOSC_DEVICE: chains whose only host byte-to-byte stage is blosc hand their frames to the
+# device in one batch (zh_blosc_decode_batch) instead of decoding them here one at a time.
+# The default follows the measurement in DESIGN.md ("Blosc frames on the device").
+BLOSC_DEVICE_DEFAULT = "1"
+
+
+class _Deferred:
+    """A store or index error of one chunk's load, kept until the chunks before it have had
+    their frames decoded: the first error in chunk order is the one a read reports."""
+
+    def __init__(self, exc):
+        self.exc = exc
+
+
+def _raise_blosc(err):
+    """A _lib.ZhError of the batched blosc decode as BloscCodec.decode raises it."""
+    if err.status == A.ZH_EUNSUPPORTED:
+        raise UnsupportedChainError(str(err)) from None
+    if err.status in (A.ZH_EDATA, A.ZH_EINVAL):
+        raise ZarrException(f"Error in decoding blosc: {err}") from None
+    raise_for(err)
 
 
 def device():
@@ -283,7 +307,7 @@ class Array:
         pb = b"".join(payload)
         return ib + pb if start else pb + ib
 
-    def _stage_shard(self, h, part_lo, part_hi, lease, full=False):
+    def _stage_shard(self, h, part_lo, part_hi, lease, full=False, collect=False):
         """StoreHandleDataProvider semantics (ShardingIndexedCodec.java:190-230, 333-357): one
         range read for the index, zh_shard_ranges for the inner chunks the part references,
         one store read per range (in parallel, straight into one pooled buffer).  The stored
@@ -294,7 +318,9 @@ class Array:
         reference's "Could not load byte data for chunk").  `full`: the part is the whole shard
         (decodePartial → chunkHandle.read() → ByteBufferDataProvider, :246-251, 301-331), so
         the shard is the file as it is — an entry beyond its bytes is an error (Q14), not a
-        zero-padded range.  Returns a ShardSource plus the buffers it points into, or None for
+        zero-padded range.  `collect` (the device blosc route): the inner chunks' frames are
+        kept as read, as pieces (offset, stored bytes, frame, None), for one batched decode of
+        the whole read.  Returns a ShardSource plus the buffers it points into, or None for
         a missing shard."""
         if not h.exists():
             return None
@@ -335,12 +361,15 @@ class Array:
         pieces = []
         if host:  # per inner chunk: undo the host codecs
             for o, nb in rs:
-                if full and o + nb > size:  # beyond the object: left out, the device reports it
+                if full and 0 <= size < o + nb:  # beyond the object: left out, the device reports it
                     continue
                 blob = h.read(o, o + nb)
                 if blob is None or len(blob) < nb:
                     continue
                 self._count_staged(nb)
+                if collect:
+                    pieces.append((o, nb, blob, None))
+                    continue
                 raw = np.frombuffer(host_bb_decode(host, blob) or b"\0", np.uint8)
                 keep.append(raw)
                 pieces.append((o, nb, raw.ctypes.data, len(raw)))
@@ -471,6 +500,10 @@ class Array:
             self.last_read_timing = {"prep_s": t0 - t_enter, "stage_s": t1 - t0,
                                      "device_s": time.perf_counter() - t1, "files": True}
             return
+        if self._blosc_device(devs):
+            self._read_blosc_device(coords, offset, shape, out_addr, flags, devs[0], parallel,
+                                    t_enter, t0)
+            return
         lease = []  # staging buffers of this read, back to the pool after the device read
         sharded = self.chain.chain["sharded"]
         try:
@@ -488,6 +521,8 @@ class Array:
             else:
                 sources = [load(c) for c in coords]
             t1 = time.perf_counter()
+            n_blosc = 0 if not self._blosc_chain() else sum(
+                0 if s is None else len(s[1].pieces) if s[0] == "pieces" else 1 for s in sources)
             keep = []
             try:
                 if sharded:  # index + pieces (or whole objects as one piece at 0)
@@ -532,7 +567,112 @@ class Array:
         finally:  # also when a store read or a host codec raised: the lease goes back
             staging_pool.give(lease)
         self.last_read_timing = {"prep_s": t0 - t_enter, "stage_s": t1 - t0,
-                                 "device_s": time.perf_counter() - t1}
+                                 "device_s": time.perf_counter() - t1,
+                                 "blosc_device_frames": 0, "blosc_host_frames": n_blosc}
+
+    def _blosc_chain(self):
+        """The chain's host byte-to-byte stages are exactly one BloscCodec (v3 or v2)."""
+        bb = self.chain.inner_host_bb if self.chain.chain["sharded"] else self.chain.host_bb
+        return len(bb) == 1 and isinstance(bb[0], BloscCodec)
+
+    def _blosc_device(self, devs):
+        return (len(devs) == 1 and self._blosc_chain() and
+                os.environ.get("ZH_BLOSC_DEVICE", BLOSC_DEVICE_DEFAULT) != "0")
+
+    def _read_blosc_device(self, coords, offset, shape, out_addr, flags, dev, parallel, t_enter,
+                           t0):
+        """_read_into for a blosc chain on one device: the store reads of every chunk (a
+        shard: its index check and per-entry range reads), one zh_blosc_decode_batch over all
+        frames of the read, then the device read over sources in the batch buffer."""
+        sharded = self.chain.chain["sharded"]
+        cs = self.metadata.chunk_shape
+
+        def load(c):
+            try:
+                h = self._handle(c)
+                if not sharded:
+                    b = h.read()
+                    if b is not None:
+                        self._count_staged(len(b))
+                    return b
+                lo = [max(o, ci * k) - ci * k for o, ci, k in zip(offset, c, cs)]
+                hi = [min(o + s, (ci + 1) * k) - ci * k
+                      for o, s, ci, k in zip(offset, shape, c, cs)]
+                full = all(a == 0 and b == k for a, b, k in zip(lo, hi, cs))
+                return self._stage_shard(h, lo, hi, None, full, collect=True)
+            except Exception as e:  # reported in chunk order, after earlier chunks' frames
+                return _Deferred(e)
+        if parallel and len(coords) > 1:
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=min(8, len(coords))) as ex:
+                sources = list(ex.map(load, coords))
+        else:
+            sources = [load(c) for c in coords]
+        t1 = time.perf_counter()
+        bad = next((k for k, s in enumerate(sources) if isinstance(s, _Deferred)), None)
+        frames = []
+        for s in sources[:bad]:
+            if s is None:
+                continue
+            frames.extend([p[2] for p in s[0].pieces] if sharded else [s])
+        views = [np.frombuffer(f if len(f) else b"\0", np.uint8) for f in frames]
+        ptr = iptr = None
+        try:
+            try:
+                ptr, rows = dev.blosc_decode_batch(
+                    [(int(v.ctypes.data), len(f)) for v, f in zip(views, frames)])
+            except _lib.ZhError as e:
+                _raise_blosc(e)
+            if bad is not None:
+                raise sources[bad].exc
+            it = iter(rows)
+            try:
+                if sharded:
+                    # the stored indexes, uploaded side by side
+                    idx = [None if s is None else s[1][0][:s[0].index_nbytes] for s in sources]
+                    ioff, pos = [], 0
+                    for a in idx:
+                        ioff.append(pos)
+                        pos += 0 if a is None else -(-len(a) // 256) * 256
+                    ibuf = np.zeros(max(1, pos), np.uint8)
+                    for a, o in zip(idx, ioff):
+                        if a is not None:
+                            ibuf[o:o + len(a)] = a
+                    iptr = dev.malloc(ibuf.nbytes, A.ZH_MALLOC_PLAIN)
+                    dev.memcpy(iptr, ibuf.ctypes.data, ibuf.nbytes, 0)
+                    shards = []
+                    for s, o in zip(sources, ioff):
+                        if s is None:
+                            shards.append(None)
+                            continue
+                        ps = []
+                        for po, pn, _, _ in s[0].pieces:
+                            doff, dn, _ = next(it)
+                            ps.append((po, pn, ptr + doff, dn))
+                        shards.append(_lib.ShardSource(iptr + o, s[0].index_nbytes,
+                                                       s[0].shard_nbytes, ps))
+                    dev.array_read_pieces(self.zmeta, shards, offset, shape, out_addr,
+                                          flags | A.ZH_SRC_DEVICE)
+                else:
+                    srcs = []
+                    for s in sources:
+                        if s is None:
+                            srcs.append((None, 0))
+                        else:
+                            doff, dn, _ = next(it)
+                            srcs.append((ptr + doff, dn))
+                    dev.array_read(self.zmeta, srcs, offset, shape, out_addr,
+                                   flags | A.ZH_SRC_DEVICE)
+            except _lib.ZhError as e:
+                raise_for(e)
+        finally:
+            dev.free(ptr)
+            dev.free(iptr)
+            del views, sources
+        self.last_read_timing = {
+            "prep_s": t0 - t_enter, "stage_s": t1 - t0, "device_s": time.perf_counter() - t1,
+            "blosc_device_frames": sum(1 for r in rows if r[2] != 1),
+            "blosc_host_frames": sum(1 for r in rows if r[2] == 1)}
 
     def readChunk(self, coords):
         """core.Array.readChunk (M/core/Array.java:167-182)."""
