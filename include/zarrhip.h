@@ -630,6 +630,52 @@ double zh_debug_blosc_kernel_ms(void);
 int64_t zh_debug_blosc_streams(const void* src, size_t srclen, int64_t* rows, int64_t cap,
                                char* err, size_t errlen);
 
+/* ---- blosc1 LZ4 frames written on the host and on the device ---------------------------
+ * The writer of the frames the decoders above read: version 2, compressor code 1 (LZ4), byte
+ * or bit shuffle (format-2 rule), blocks of at most 64 KiB (a larger configured block size is
+ * clamped), split into typesize streams when the shuffle is the byte shuffle, typesize <= 16
+ * and blocksize / typesize >= 128.  A stream LZ4 would not shrink is stored raw; a frame that
+ * would pass nbytes + 16 is written MEMCPYED, so cbytes <= nbytes + 16 always.  The bytes are
+ * a pure function of (input, typesize, shuffle, block size): the host call and the batch call
+ * give the same frame. */
+typedef struct zh_blosc_enc_params {
+  int32_t typesize;   /* 1..255                                */
+  int32_t shuffle;    /* 0 none, 1 byte, 2 bit                 */
+  int32_t blocksize;  /* 0: default (16 KiB); above 64 KiB: 64 KiB */
+} zh_blosc_enc_params;
+
+typedef struct zh_blosc_enc_frame {
+  const void* src;   /* raw bytes: device memory for the batch call            */
+  int64_t nbytes;
+  int64_t dst_off;   /* out: place of the frame in dst, 16-byte aligned        */
+  int64_t cbytes;    /* out: size of the frame                                 */
+  int32_t status;    /* out: ZH_OK or this frame's error                       */
+} zh_blosc_enc_frame;
+
+/* Host, no device: one frame.  dst == NULL: *cbytes = the bound nbytes + 16 (cap must reach
+ * it otherwise).  typesize outside 1..255 (or another bad parameter) → ZH_EINVAL. */
+int zh_blosc_compress(const void* src, size_t n, const zh_blosc_enc_params* params, void* dst,
+                      size_t cap, size_t* cbytes, char* err, size_t errlen);
+
+/* Host memory a batch needs for its frames: the sum of nbytes + 16, each rounded up to 16
+ * bytes; or -zh_status. */
+int64_t zh_blosc_encode_bound(const zh_blosc_enc_frame* frames, int64_t n,
+                              const zh_blosc_enc_params* params);
+
+/* Sources in device memory; the frames arrive in host memory dst (dstcap >= the bound) at
+ * dst_off, cbytes long, compressed by one kernel (one workgroup per block, one wavefront per
+ * stream), laid out by a second, and copied back through the context's page-locked ring: only
+ * the compressed bytes and the size tables cross PCIe.  Runs on `stream` (NULL: the
+ * context's) and waits.  Batches are worked off in slabs of at most 128 MiB of raw bytes (a
+ * larger frame is its own slab), which bounds the device memory of a call. */
+int zh_blosc_encode_batch(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
+                          const zh_blosc_enc_params* params, void* dst, int64_t dstcap,
+                          void* stream, char* err, size_t errlen);
+
+/* Diagnostic: milliseconds the two kernels of the last successful zh_blosc_encode_batch took,
+ * by device events around their launches, summed over its slabs (-1: none yet). */
+double zh_debug_blosc_encode_kernel_ms(void);
+
 /* ---- host byte-to-byte stage: zstd frames (RFC 8878) ------------------------------
  * Replaces zstd-jni inside ZstdCodec.decode (M/core/codec/core/ZstdCodec.java:14-22) and the
  * zstd compressor of blosc frames (BloscCodec.java; CodecBuilder.withBlosc() defaults to

@@ -1,0 +1,284 @@
+// zh_blosc_enc.h — the blosc1 LZ4 frame writer shared by the host and the device.
+//
+// The writer emits what zh_blosc_streams.h reads (build_table is the contract): version 2,
+// versionlz 1, compressor code 1 (LZ4), flags 0x01 byte shuffle / 0x04 bit shuffle (format-2
+// rule: kShufBit2) / 0x10 blocks not split, the block starts, then per stream an int32 csize and
+// the payload.  This header holds what both sides need, and nothing that needs a device:
+//   * make_layout: block size, split rule and flags of a frame of n bytes;
+//   * shuffled_byte_at: byte o of the shuffled block, read from the raw block (the inverse of
+//     zh_bs::unshuffle_byte_at);
+//   * encode_stream: one stream (s, n) -> LZ4 bytes, written once over a lane policy W.  The
+//     algorithm is stated for the 64 lanes of a wave: at cursor p lane l looks at p + l, hashes
+//     4 bytes, reads its candidate from the table, checks the 4 bytes (failing that, the 4
+//     bytes one position back: a run, which the table cannot know inside one step); the lowest
+//     matching lane wins, the match is extended 64 bytes per step, the sequence is written, the
+//     table takes the positions before the new cursor, the cursor moves behind the match.
+//     Lookups of one step see the table as the previous step left it, and two lanes that hash
+//     to one slot
+//     resolve by maximum (the slot keeps the highest position + 1), so the output is a pure
+//     function of (input bytes, n).  W:
+//         void     clear(uint32_t* table)
+//         uint32_t find(s, p, lim, table, &ref)   lowest lane whose candidate matches (64: none);
+//                                                 keeps every lane's hash for insert
+//         void     insert(p, end, table)          table[hash] = max(., q + 1) for p <= q < end
+//         uint32_t extend(s, a, b, maxn)          leading k < maxn with s[a + k] == s[b + k]
+//         void     copy(d, s, n)  /  lenbytes(d, v)  /  put(d, byte)
+//     HostLanes loops over the 64 lane indices; the kernel's WaveLanes (zh_blosc_enc_kernels.hip)
+//     is one wave.  A stream whose encoding would reach its raw size returns n before writing
+//     past out[n - 1]: the caller stores it raw;
+//   * compress_frame: the whole frame on the host with HostLanes (zh_blosc_compress, the
+//     kernel's byte-for-byte oracle, tools/blosc_enc_check.cpp under sanitizers).
+// LZ4 end rules (liblz4 decodes the streams): the last 5 bytes are literals, no match starts
+// within the last 12 bytes, a stream shorter than 13 bytes is never encoded, offsets are
+// 1..65535 (a stream is at most 64 KiB).
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "zh_blosc_streams.h"
+
+namespace zh_be {
+
+constexpr uint32_t kMaxBlock = 64u << 10;      // kLdsBlock of the decoder: blocks stay in LDS
+constexpr uint32_t kDefaultBlock = 16u << 10;  // DESIGN.md "Blosc frames encoded on the device"
+constexpr uint32_t kHashBits = 10;
+constexpr uint32_t kHashSize = 1u << kHashBits;  // uint32 slots per wave: position + 1, 0 empty
+constexpr size_t kMaxFrame = 0x7fffffffu - 16;   // blosc1: nbytes + 16 fits an int32
+
+struct Layout {
+  uint32_t typesize = 1, shuffle = 0 /* zh_bs::Shuffle */, blocksize = 0, nblocks = 0, flags = 0;
+  bool split = false;
+};
+
+inline int make_layout(size_t n, const zh_blosc_enc_params* p, Layout* L) {
+  if (!p || p->typesize < 1 || p->typesize > 255 || p->shuffle < 0 || p->shuffle > 2 ||
+      p->blocksize < 0 || n > kMaxFrame)
+    return ZH_EINVAL;
+  const uint32_t ts = (uint32_t)p->typesize;
+  size_t bs = p->blocksize > 0 ? (size_t)p->blocksize : kDefaultBlock;
+  if (bs > kMaxBlock) bs = kMaxBlock;  // blosc treats the configured block size as advice
+  if (bs > n) bs = n;
+  if (bs > ts) bs = bs / ts * ts;
+  L->typesize = ts;
+  L->shuffle = p->shuffle == 1 ? zh_bs::kShufByte : (p->shuffle == 2 ? zh_bs::kShufBit2
+                                                                      : zh_bs::kShufNone);
+  L->blocksize = (uint32_t)bs;
+  L->nblocks = bs ? (uint32_t)((n + bs - 1) / bs) : 0;
+  L->split = p->shuffle == 1 && ts <= 16 && bs / ts >= 128;
+  L->flags = (1u << 5) | (p->shuffle == 1 ? 0x01u : 0u) | (p->shuffle == 2 ? 0x04u : 0u) |
+             (L->split ? 0u : 0x10u);
+  return ZH_OK;
+}
+
+// Size and stream count of block k (a leftover block is never split).
+inline uint32_t block_size(const Layout& L, size_t n, uint32_t k) {
+  const size_t rest = n - (size_t)k * L.blocksize;
+  return rest < L.blocksize ? (uint32_t)rest : L.blocksize;
+}
+inline uint32_t block_streams(const Layout& L, uint32_t bsz) {
+  return L.split && bsz == L.blocksize ? L.typesize : 1;
+}
+
+// Byte o of the shuffled form of the raw block `in` of `size` bytes.
+ZH_BS_HD uint8_t shuffled_byte_at(const uint8_t* in, uint32_t o, uint32_t size, uint32_t ts,
+                                  uint32_t shuffle) {
+  if (shuffle == zh_bs::kShufByte) {
+    const uint32_t ne = size / ts;
+    if (o >= ne * ts) return in[o];
+    return in[(o % ne) * ts + o / ne];
+  }
+  if (shuffle == zh_bs::kShufBit2 || shuffle == zh_bs::kShufBit3) {
+    const uint32_t ne = zh_bs::bitshuffle_elems(size, ts, shuffle);
+    if (o >= ne * ts) return in[o];
+    const uint32_t rowb = ne / 8, row = o / rowb, p = o % rowb, j = row / 8, k = row % 8;
+    uint32_t v = 0;
+    for (uint32_t m = 0; m < 8; m++) v |= ((in[(size_t)(8 * p + m) * ts + j] >> k) & 1u) << m;
+    return (uint8_t)v;
+  }
+  return in[o];
+}
+
+ZH_BS_HD uint32_t ld32(const uint8_t* p) {
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+ZH_BS_HD uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - kHashBits); }
+// bytes a length beyond the token's 4 bits takes (0 below 15)
+ZH_BS_HD uint32_t len_extra(uint32_t v) { return v >= 15 ? (v - 15) / 255 + 1 : 0; }
+
+// The 64 lanes as a loop: the host form of the lane policy.
+struct HostLanes {
+  uint32_t h[64];
+  void clear(uint32_t* table) {
+    for (uint32_t i = 0; i < kHashSize; i++) table[i] = 0;
+  }
+  uint32_t find(const uint8_t* s, uint32_t p, uint32_t lim, const uint32_t* table,
+                uint32_t* ref) {
+    uint32_t best = 64;
+    for (uint32_t l = 0; l < 64; l++) {
+      const uint32_t q = p + l;
+      if (q > lim) break;
+      const uint32_t v = ld32(s + q);
+      h[l] = hash4(v);
+      const uint32_t c = table[h[l]];
+      if (best != 64) continue;
+      if (c != 0 && ld32(s + c - 1) == v) {
+        best = l;
+        *ref = c - 1;
+      } else if (q >= 1 && ld32(s + q - 1) == v) {  // a run: the table only knows earlier steps
+        best = l;
+        *ref = q - 1;
+      }
+    }
+    return best;
+  }
+  void insert(uint32_t p, uint32_t end, uint32_t* table) {
+    for (uint32_t l = 0; l < 64 && p + l < end; l++)
+      if (table[h[l]] < p + l + 1) table[h[l]] = p + l + 1;
+  }
+  uint32_t extend(const uint8_t* s, uint32_t a, uint32_t b, uint32_t maxn) {
+    uint32_t k = 0;
+    while (k < maxn && s[a + k] == s[b + k]) k++;
+    return k;
+  }
+  void copy(uint8_t* d, const uint8_t* s, uint32_t n) {
+    for (uint32_t k = 0; k < n; k++) d[k] = s[k];
+  }
+  void lenbytes(uint8_t* d, uint32_t v) {
+    const uint32_t nfull = v / 255;
+    for (uint32_t k = 0; k < nfull; k++) d[k] = 255;
+    d[nfull] = (uint8_t)(v % 255);
+  }
+  void put(uint8_t* d, uint32_t b) { *d = (uint8_t)b; }
+};
+
+// One LZ4 sequence at out + o: token, literal length, literals, then (ml != 0) offset and match
+// length.  The caller has checked the room.
+template <class W>
+ZH_BS_HD uint32_t put_sequence(uint8_t* out, uint32_t o, const uint8_t* lits, uint32_t lit,
+                               uint32_t off, uint32_t ml, W& w) {
+  const uint32_t mcode = ml ? ml - 4 : 0;
+  w.put(out + o, ((lit < 15 ? lit : 15u) << 4) | (mcode < 15 ? mcode : 15u));
+  o++;
+  if (lit >= 15) {
+    w.lenbytes(out + o, lit - 15);
+    o += len_extra(lit);
+  }
+  w.copy(out + o, lits, lit);
+  o += lit;
+  if (ml) {
+    w.put(out + o, off & 255u);
+    w.put(out + o + 1, off >> 8);
+    o += 2;
+    if (mcode >= 15) {
+      w.lenbytes(out + o, mcode - 15);
+      o += len_extra(mcode);
+    }
+  }
+  return o;
+}
+
+// The stream (s, n) as LZ4 into out (room for n bytes); table: kHashSize slots.  Returns the
+// encoded size, or n when the encoding would reach n (out then holds nothing of use: the
+// caller stores the stream raw).
+template <class W>
+ZH_BS_HD uint32_t encode_stream(const uint8_t* s, uint32_t n, uint8_t* out, uint32_t* table,
+                                W& w) {
+  if (n < 13 || n > kMaxBlock) return n;
+  w.clear(table);
+  const uint32_t lim = n - 13;  // the last position a match may start at
+  const uint32_t mend = n - 5;  // a match ends at or before this
+  uint32_t p = 0, a = 0, o = 0;
+  while (p <= lim) {
+    uint32_t ref = 0;
+    const uint32_t lane = w.find(s, p, lim, table, &ref);
+    if (lane == 64) {
+      w.insert(p, lim + 1, table);
+      p += 64;
+      continue;
+    }
+    const uint32_t m = p + lane;
+    const uint32_t ml = 4 + w.extend(s, ref + 4, m + 4, mend - (m + 4));
+    const uint32_t lit = m - a;
+    const uint32_t need = 1 + len_extra(lit) + lit + 2 + len_extra(ml - 4);
+    if (o + need >= n) return n;
+    o = put_sequence(out, o, s + a, lit, m - ref, ml, w);
+    w.insert(p, m + ml < lim + 1 ? m + ml : lim + 1, table);
+    p = a = m + ml;
+  }
+  const uint32_t lit = n - a;
+  if (o + 1 + len_extra(lit) + lit >= n) return n;
+  return put_sequence(out, o, s + a, lit, 0, 0, w);
+}
+
+inline void wr32(uint8_t* p, uint32_t v) {
+  p[0] = (uint8_t)v, p[1] = (uint8_t)(v >> 8), p[2] = (uint8_t)(v >> 16), p[3] = (uint8_t)(v >> 24);
+}
+
+inline void put_header(uint8_t* d, const Layout& L, uint32_t flags, size_t n, size_t cbytes) {
+  d[0] = 2, d[1] = 1, d[2] = (uint8_t)flags, d[3] = (uint8_t)L.typesize;
+  wr32(d + 4, (uint32_t)n);
+  wr32(d + 8, L.blocksize);
+  wr32(d + 12, (uint32_t)cbytes);
+}
+// flags of a frame written MEMCPYED (the shuffle bits stay as configured; readers ignore them)
+inline uint32_t memcpyed_flags(const Layout& L) { return (L.flags & ~0x10u) | 0x02u; }
+
+// One frame on the host.  dst == nullptr: *cbytes = the bound n + 16.  tmp, scratch: one block
+// each (min(blocksize, n) bytes); table: kHashSize slots.
+inline int compress_frame(const uint8_t* src, size_t n, const zh_blosc_enc_params* prm,
+                          uint8_t* dst, size_t cap, size_t* cbytes, const char** msg) {
+  Layout L;
+  if (make_layout(n, prm, &L) != ZH_OK || (n > 0 && !src)) {
+    *msg = "zh_blosc_compress: typesize 1..255, shuffle 0..2, blocksize >= 0, at most 2 GiB";
+    return ZH_EINVAL;
+  }
+  if (!dst) {
+    *cbytes = n + 16;
+    return ZH_OK;
+  }
+  if (cap < n + 16) {
+    *msg = "zh_blosc_compress: destination smaller than nbytes + 16";
+    return ZH_EINVAL;
+  }
+  size_t pos = 16 + 4 * (size_t)L.nblocks;
+  bool fits = n > 0 && pos <= n + 16;  // tiny blocks: the block starts alone can pass the bound
+  if (fits) {
+    uint8_t* tmp = new uint8_t[L.blocksize];
+    uint8_t* scratch = new uint8_t[L.blocksize];
+    uint32_t* table = new uint32_t[kHashSize];
+    HostLanes w;
+    for (uint32_t k = 0; k < L.nblocks && fits; k++) {
+      const uint32_t bsz = block_size(L, n, k), ns = block_streams(L, bsz), neb = bsz / ns;
+      const uint8_t* in = src + (size_t)k * L.blocksize;
+      for (uint32_t o = 0; o < bsz; o++) tmp[o] = shuffled_byte_at(in, o, bsz, L.typesize, L.shuffle);
+      wr32(dst + 16 + 4 * (size_t)k, (uint32_t)pos);
+      for (uint32_t si = 0; si < ns && fits; si++) {
+        const uint8_t* st = tmp + (size_t)si * neb;
+        const uint32_t cs = encode_stream(st, neb, scratch, table, w);
+        if (pos + 4 + cs > n + 16) {
+          fits = false;
+          break;
+        }
+        wr32(dst + pos, cs);
+        const uint8_t* from = cs == neb ? st : scratch;
+        for (uint32_t q = 0; q < cs; q++) dst[pos + 4 + q] = from[q];
+        pos += 4 + (size_t)cs;
+      }
+    }
+    delete[] table;
+    delete[] scratch;
+    delete[] tmp;
+  }
+  if (!fits) {  // header alone (n == 0), or the raw bytes behind it
+    put_header(dst, L, memcpyed_flags(L), n, n + 16);
+    for (size_t q = 0; q < n; q++) dst[16 + q] = src[q];
+    *cbytes = n + 16;
+    return ZH_OK;
+  }
+  put_header(dst, L, L.flags, n, pos);
+  *cbytes = pos;
+  return ZH_OK;
+}
+
+}  // namespace zh_be

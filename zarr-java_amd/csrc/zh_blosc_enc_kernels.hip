@@ -1,0 +1,551 @@
+// zh_blosc_enc_kernels.hip — blosc1 LZ4 frames written on the device, a batch at a time
+// (zh_blosc_compress / zh_blosc_encode_bound / zh_blosc_encode_batch).
+//
+// The raw bytes are in device memory (zh_array_write's chunk buffers); the frames go to the host.
+//   blosc_encode_kernel<CAP>   grid: one workgroup (4 waves) per block of at most CAP bytes (16,
+//           32 or 64 KiB: the smallest that holds the slab's blocks).  All 256 threads load the
+//           block into LDS in its shuffled form (16-byte loads where the source is aligned; the
+//           byte shuffle scatters the 16 bytes, the bit shuffle gathers 8 elements per thread).
+//           After the barrier the block is read-only; wave w compresses streams w, w+4, ... with
+//           zh_be::encode_stream over WaveLanes, its hash table (kHashSize slots) in LDS next to
+//           the block, into its own region of a scratch buffer in global memory, and stores the
+//           stream's csize.  A stream LZ4 does not shrink is copied raw into that region.  A wave
+//           writes only its own region, so the output needs no ordering between waves; within
+//           the wave the table is read and updated by different lanes in different steps, and a
+//           wave's LDS operations complete in order (the fence pair only keeps the compiler
+//           from moving them).  Two lanes of one step that hash to the same slot resolve by an
+//           LDS atomic max: never by whichever store lands last.
+//   host    one small copy brings the csize table back; a prefix sum lays the frames out
+//           (a frame past nbytes + 16 becomes MEMCPYED) and builds one copy job per stream;
+//   blosc_gather_kernel   one workgroup per job: an optional 4-byte word (the csize), then the
+//           bytes, from scratch (streams), from the raw source (MEMCPYED frames) or from the
+//           uploaded headers and block starts, into one compact buffer of complete frames;
+//   D2H     the compact buffer through the context's page-locked out ring into host memory.
+// Slabs of at most kSlabBytes of raw input bound the scratch and the compact buffer.
+// Every job and block row is built on the host from validated sizes; the csize table is checked
+// against the stream sizes before it lays anything out.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <vector>
+
+#include "zh_blosc_enc.h"
+#include "zh_ctx.h"
+
+namespace {
+
+constexpr int kWaves = 4;
+constexpr int kThreads = kWaves * 64;
+constexpr int64_t kSlabBytes = (int64_t)128 << 20;
+constexpr uint32_t kJobBytes = 64u << 10;  // a MEMCPYED frame is copied in pieces of this size
+
+struct EncBlock {
+  uint64_t src;      // device address of the raw block
+  uint64_t scratch;  // offset of the block's region in the scratch buffer
+  uint32_t size, typesize, shuffle, nstreams, first_stream, pad;
+};
+struct GatherJob {
+  uint64_t src, dst;  // device addresses
+  uint32_t n, word, has_word, pad;
+};
+
+// The lane policy of zh_be::encode_stream for one wave.
+struct WaveLanes {
+  uint32_t lane, h;
+
+  // Between two steps only the table in LDS is read by other lanes than wrote it: the wave
+  // waits for its LDS operations, never for its stores to the scratch (nothing reads those back).
+  __device__ static void order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+  // Before the raw copy overwrites what the abandoned encoding stored in the same region.
+  __device__ static void drain_stores() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __device__ void clear(uint32_t* table) {
+    for (uint32_t i = lane; i < zh_be::kHashSize; i += 64) table[i] = 0;
+    order();
+  }
+  __device__ uint32_t find(const uint8_t* s, uint32_t p, uint32_t lim, const uint32_t* table,
+                           uint32_t* ref) {
+    const uint32_t q = p + lane;
+    uint32_t c = 0;
+    bool ok = false;
+    if (q <= lim) {
+      const uint32_t v = zh_be::ld32(s + q);
+      h = zh_be::hash4(v);
+      c = table[h];
+      ok = c != 0 && zh_be::ld32(s + c - 1) == v;
+      if (!ok && q >= 1 && zh_be::ld32(s + q - 1) == v) ok = true, c = q;  // a run
+    }
+    const unsigned long long b = __ballot(ok);
+    if (!b) return 64;
+    const int first = __builtin_ctzll(b);
+    *ref = (uint32_t)__builtin_amdgcn_readlane((int)c, first) - 1;
+    return (uint32_t)first;
+  }
+  __device__ void insert(uint32_t p, uint32_t end, uint32_t* table) {
+    if (p + lane < end) atomicMax(&table[h], p + lane + 1);
+    order();
+  }
+  __device__ uint32_t extend(const uint8_t* s, uint32_t a, uint32_t b, uint32_t maxn) {
+    for (uint32_t k0 = 0; k0 < maxn; k0 += 64) {
+      const uint32_t k = k0 + lane;
+      const bool differ = k >= maxn || s[a + k] != s[b + k];
+      const unsigned long long m = __ballot(differ);
+      if (m) return k0 + (uint32_t)__builtin_ctzll(m);
+    }
+    return maxn;
+  }
+  __device__ void copy(uint8_t* d, const uint8_t* s, uint32_t n) {
+    for (uint32_t k = lane; k < n; k += 64) d[k] = s[k];
+  }
+  __device__ void lenbytes(uint8_t* d, uint32_t v) {
+    const uint32_t nfull = v / 255;
+    for (uint32_t k = lane; k <= nfull; k += 64) d[k] = k < nfull ? 255 : (uint8_t)(v % 255);
+  }
+  __device__ void put(uint8_t* d, uint32_t b) {
+    if (lane == 0) *d = (uint8_t)b;
+  }
+};
+
+// 16 bytes of the raw block at q0 (cnt of them valid) as four words.
+__device__ void load16(const uint8_t* __restrict__ src, uint32_t q0, uint32_t cnt, bool al,
+                       uint32_t v[4]) {
+  if (al && cnt == 16) {
+    const uint4 x = *(const uint4*)(src + q0);
+    v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
+    return;
+  }
+  v[0] = v[1] = v[2] = v[3] = 0;
+  for (uint32_t k = 0; k < cnt; k++) v[k >> 2] |= (uint32_t)src[q0 + k] << (8 * (k & 3));
+}
+
+// The raw block into LDS in its shuffled form (zh_be::shuffled_byte_at, restated per shuffle so
+// that the source is read once, in wide loads).
+__device__ void load_block(uint8_t* lds, const uint8_t* __restrict__ src, const EncBlock& b,
+                           uint32_t tid) {
+  const bool al = (((uintptr_t)src) & 15) == 0;
+  const uint32_t size = b.size, ts = b.typesize;
+  if (b.shuffle == zh_bs::kShufByte && ts > 1) {
+    const uint32_t ne = size / ts, lim = ne * ts;
+    for (uint32_t q0 = tid * 16; q0 < size; q0 += kThreads * 16) {
+      const uint32_t cnt = size - q0 < 16u ? size - q0 : 16u;
+      uint32_t v[4];
+      load16(src, q0, cnt, al, v);
+      uint32_t e = q0 / ts, j = q0 % ts;
+      for (uint32_t k = 0; k < cnt; k++) {
+        const uint32_t q = q0 + k;
+        lds[q < lim ? j * ne + e : q] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
+        if (++j == ts) j = 0, e++;
+      }
+    }
+    return;
+  }
+  if (b.shuffle == zh_bs::kShufBit2 || b.shuffle == zh_bs::kShufBit3) {
+    const uint32_t ne = zh_bs::bitshuffle_elems(size, ts, b.shuffle), rowb = ne / 8;
+    // unit (j, p): byte j of elements 8p .. 8p+7 -> bit rows j*8 .. j*8+7, byte p
+    for (uint32_t u = tid; u < ts * rowb; u += kThreads) {
+      const uint32_t j = u / rowb, p = u % rowb;
+      uint32_t x[8];
+      for (uint32_t m = 0; m < 8; m++) x[m] = src[(size_t)(8 * p + m) * ts + j];
+      for (uint32_t k = 0; k < 8; k++) {
+        uint32_t o = 0;
+        for (uint32_t m = 0; m < 8; m++) o |= ((x[m] >> k) & 1u) << m;
+        lds[(j * 8 + k) * rowb + p] = (uint8_t)o;
+      }
+    }
+    for (uint32_t q = ne * ts + tid; q < size; q += kThreads) lds[q] = src[q];
+    return;
+  }
+  for (uint32_t q0 = tid * 16; q0 < size; q0 += kThreads * 16) {
+    const uint32_t cnt = size - q0 < 16u ? size - q0 : 16u;
+    uint32_t v[4];
+    load16(src, q0, cnt, al, v);
+    if (cnt == 16) {
+      *(uint4*)(lds + q0) = make_uint4(v[0], v[1], v[2], v[3]);
+    } else {
+      for (uint32_t k = 0; k < cnt; k++) lds[q0 + k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
+    }
+  }
+}
+
+// CAP: the largest block of the launch.  The streams are latency-bound (one dependent step per
+// LZ4 sequence), so what LDS a launch does not need buys resident waves: 16, 32 and 64 KiB of
+// block plus the 16 KiB of tables are 5, 3 and 2 workgroups per CU.
+template <uint32_t CAP>
+__global__ __launch_bounds__(kThreads) void blosc_encode_kernel(
+    const EncBlock* __restrict__ blocks, uint8_t* __restrict__ scratch,
+    uint32_t* __restrict__ csizes) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[CAP];
+  __shared__ uint32_t tables[kWaves][zh_be::kHashSize];
+  const EncBlock b = blocks[blockIdx.x];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  load_block(lds, (const uint8_t*)b.src, b, threadIdx.x);
+  __syncthreads();
+  WaveLanes w;
+  w.lane = lane;
+  w.h = 0;
+  const uint32_t neb = b.size / b.nstreams;
+  for (uint32_t s = wave; s < b.nstreams; s += kWaves) {
+    const uint8_t* st = lds + (size_t)s * neb;
+    uint8_t* out = scratch + b.scratch + (size_t)s * neb;
+    const uint32_t cs = zh_be::encode_stream(st, neb, out, tables[wave], w);
+    if (cs == neb) {  // stored raw: the shuffled bytes themselves
+      WaveLanes::drain_stores();
+      w.copy(out, st, neb);
+    }
+    if (lane == 0) csizes[b.first_stream + s] = cs;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void blosc_gather_kernel(
+    const GatherJob* __restrict__ jobs) {
+  const GatherJob j = jobs[blockIdx.x];
+  const uint8_t* s = (const uint8_t*)j.src;
+  uint8_t* d = (uint8_t*)j.dst;
+  const uint32_t t = threadIdx.x;
+  if (j.has_word) {
+    if (t < 4) d[t] = (uint8_t)(j.word >> (8 * t));
+    d += 4;
+  }
+  uint32_t n = j.n;
+  uint32_t head = (uint32_t)((16 - (((uintptr_t)d) & 15)) & 15);
+  if (head > n) head = n;
+  if (t < head) d[t] = s[t];
+  s += head, d += head, n -= head;
+  const uint32_t nv = n / 16;
+  const uint32_t sh = (uint32_t)(((uintptr_t)s) & 3);
+  if ((((uintptr_t)s) & 15) == 0) {
+    for (uint32_t i = t; i < nv; i += kThreads) ((uint4*)d)[i] = ((const uint4*)s)[i];
+  } else {
+    // the source is not aligned with the destination: aligned words, shifted into place.  The
+    // fifth word holds at least one byte of the range when sh != 0, and is not read otherwise.
+    const uint32_t* s4 = (const uint32_t*)(s - sh);
+    for (uint32_t i = t; i < nv; i += kThreads) {
+      uint32_t x[5];
+      for (int k = 0; k < 4; k++) x[k] = s4[4 * i + k];
+      x[4] = sh ? s4[4 * i + 4] : 0u;
+      uint32_t y[4];
+      for (int k = 0; k < 4; k++) y[k] = sh ? __builtin_amdgcn_alignbyte(x[k + 1], x[k], sh) : x[k];
+      ((uint4*)d)[i] = make_uint4(y[0], y[1], y[2], y[3]);
+    }
+  }
+  for (uint32_t q = nv * 16 + t; q < n; q += kThreads) d[q] = s[q];
+}
+
+void put_err(char* err, size_t errlen, const char* msg) {
+  if (err && errlen) {
+    strncpy(err, msg, errlen - 1);
+    err[errlen - 1] = 0;
+  }
+}
+
+std::atomic<double> g_last_enc_ms{-1.0};
+
+inline int64_t up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+// Through the context's page-locked rings, one slot at a time in flight per ring slot.
+struct Ring {
+  zh_ctx* ctx;
+  hipStream_t s;
+  size_t slot_bytes = 0;
+  std::vector<hipEvent_t> ev;
+
+  int init(zh_ctx* c, hipStream_t st) {
+    ctx = c, s = st;
+    int lanes;
+    int64_t window;
+    const int rc = zh::pipe_out_ring(ctx, &lanes, &window);
+    if (rc != ZH_OK) return rc;
+    slot_bytes = (size_t)window;
+    ev.assign(ctx->ring_out.size(), nullptr);
+    for (auto& e : ev)
+      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return ZH_EHIP;
+    return ev.empty() || slot_bytes == 0 ? ZH_EHIP : ZH_OK;
+  }
+  ~Ring() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  // device -> host memory, the copies pipelined over the out ring's slots; returns when done
+  bool d2h(uint8_t* h, const uint8_t* d, size_t n) {
+    const size_t nslots = ev.size(), nchunks = (n + slot_bytes - 1) / slot_bytes;
+    auto land = [&](size_t i) {
+      if (hipEventSynchronize(ev[i % nslots]) != hipSuccess) return false;
+      const size_t off = i * slot_bytes;
+      memcpy(h + off, ctx->ring_out[i % nslots], std::min(slot_bytes, n - off));
+      return true;
+    };
+    for (size_t i = 0; i < nchunks; i++) {
+      if (i >= nslots && !land(i - nslots)) return false;
+      const size_t off = i * slot_bytes;
+      if (hipMemcpyAsync(ctx->ring_out[i % nslots], d + off, std::min(slot_bytes, n - off),
+                         hipMemcpyDeviceToHost, s) != hipSuccess ||
+          hipEventRecord(ev[i % nslots], s) != hipSuccess)
+        return false;
+    }
+    for (size_t i = nchunks > nslots ? nchunks - nslots : 0; i < nchunks; i++)
+      if (!land(i)) return false;
+    return true;
+  }
+  // host tables -> device through the in ring (small: one slot, reused)
+  bool h2d(uint8_t* d, const uint8_t* h, size_t n) {
+    for (size_t off = 0; off < n; off += slot_bytes) {
+      const size_t take = std::min(slot_bytes, n - off);
+      memcpy(ctx->ring_in[0], h + off, take);
+      if (hipMemcpyAsync(d + off, ctx->ring_in[0], take, hipMemcpyHostToDevice, s) != hipSuccess ||
+          hipStreamSynchronize(s) != hipSuccess)
+        return false;
+    }
+    return true;
+  }
+};
+
+struct FramePlan {
+  zh_be::Layout L;
+  int64_t first_block = 0, first_stream = 0, nstreams = 0;  // within the slab
+  bool raw_only = false;  // the block starts alone pass the bound: MEMCPYED without a launch
+};
+
+// One slab [f0, f1) of the batch; *pos: the running offset in dst.
+int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, zh_blosc_enc_frame* frames, int64_t f0,
+                int64_t f1, const zh_blosc_enc_params* prm, uint8_t* dst, int64_t* pos,
+                double* kernel_ms) {
+  std::vector<FramePlan> plan((size_t)(f1 - f0));
+  std::vector<EncBlock> blocks;
+  std::vector<uint32_t> stream_raw;  // raw size per stream
+  int64_t scratch_total = 0, compact_cap = 0, meta_cap = 0, njobs_cap = 0;
+  for (int64_t i = f0; i < f1; i++) {
+    FramePlan& fp = plan[(size_t)(i - f0)];
+    const size_t n = (size_t)frames[i].nbytes;
+    (void)zh_be::make_layout(n, prm, &fp.L);  // validated by the caller
+    fp.first_block = (int64_t)blocks.size();
+    fp.first_stream = (int64_t)stream_raw.size();
+    fp.raw_only = 4 * (size_t)fp.L.nblocks > n;
+    for (uint32_t k = 0; k < fp.L.nblocks && !fp.raw_only; k++) {
+      EncBlock b;
+      b.size = zh_be::block_size(fp.L, n, k);
+      b.nstreams = zh_be::block_streams(fp.L, b.size);
+      b.src = (uint64_t)(uintptr_t)frames[i].src + (uint64_t)k * fp.L.blocksize;
+      b.scratch = (uint64_t)scratch_total;
+      b.typesize = fp.L.typesize, b.shuffle = fp.L.shuffle;
+      b.first_stream = (uint32_t)stream_raw.size();
+      b.pad = 0;
+      for (uint32_t q = 0; q < b.nstreams; q++) stream_raw.push_back(b.size / b.nstreams);
+      blocks.push_back(b);
+      scratch_total += up(b.size, 16);
+    }
+    fp.nstreams = (int64_t)stream_raw.size() - fp.first_stream;
+    compact_cap += up((int64_t)n + 16, 16);
+    meta_cap += 16 + (fp.raw_only ? 0 : 4 * (int64_t)fp.L.nblocks);
+    njobs_cap += 1 + std::max<int64_t>(fp.nstreams, ((int64_t)n + kJobBytes - 1) / kJobBytes);
+  }
+  if (blocks.size() > (size_t)zh::kIntMax || stream_raw.size() > (size_t)zh::kIntMax ||
+      njobs_cap > zh::kIntMax)
+    return ZH_EINVAL;
+
+  // device memory: [blocks | csizes | jobs | meta | scratch | compact]
+  const size_t o_blocks = 0;
+  const size_t o_cs = (size_t)up((int64_t)(blocks.size() * sizeof(EncBlock)), 256);
+  const size_t o_jobs = o_cs + (size_t)up((int64_t)stream_raw.size() * 4, 256);
+  const size_t o_meta = o_jobs + (size_t)up(njobs_cap * (int64_t)sizeof(GatherJob), 256);
+  const size_t o_scratch = o_meta + (size_t)up(meta_cap, 256);
+  const size_t o_compact = o_scratch + (size_t)up(scratch_total, 256);
+  const size_t need = o_compact + (size_t)compact_cap + 256;
+  void* dmem = nullptr;
+  size_t got = 0;
+  if (zh::ctx_alloc(ctx, need, &dmem, &got) != hipSuccess) {
+    (void)hipGetLastError();
+    return ZH_ENOMEM;
+  }
+  uint8_t* d8 = (uint8_t*)dmem;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (auto& e : ev) (void)hipEventCreate(&e);
+  const bool timed = ev[0] && ev[1] && ev[2] && ev[3];
+  int rc = ZH_OK;
+  std::vector<uint32_t> cs(stream_raw.size(), 0);
+  if (!blocks.empty()) {
+    if (!ring.h2d(d8 + o_blocks, (const uint8_t*)blocks.data(), blocks.size() * sizeof(EncBlock)))
+      rc = ZH_EHIP;
+    if (rc == ZH_OK) {
+      if (timed) (void)hipEventRecord(ev[0], s);
+      uint32_t cap = 0;
+      for (const EncBlock& b : blocks) cap = std::max(cap, b.size);
+      auto kernel = cap <= (16u << 10)   ? blosc_encode_kernel<(16u << 10)>
+                    : cap <= (32u << 10) ? blosc_encode_kernel<(32u << 10)>
+                                         : blosc_encode_kernel<zh_be::kMaxBlock>;
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks.size()), dim3(kThreads), 0, s,
+                         (const EncBlock*)(d8 + o_blocks), d8 + o_scratch,
+                         (uint32_t*)(d8 + o_cs));
+      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
+      if (timed) (void)hipEventRecord(ev[1], s);
+    }
+    if (rc == ZH_OK && !ring.d2h((uint8_t*)cs.data(), d8 + o_cs, cs.size() * 4)) rc = ZH_EHIP;
+    // the table lays out device copies: nothing in it may pass its stream's raw size
+    for (size_t k = 0; k < cs.size() && rc == ZH_OK; k++)
+      if (cs[k] == 0 || cs[k] > stream_raw[k]) rc = ZH_EHIP;
+  }
+
+  // layout: the frames side by side in the compact buffer, each 16-byte aligned
+  std::vector<GatherJob> jobs;
+  std::vector<uint8_t> meta;
+  int64_t cpos = 0;
+  if (rc == ZH_OK) {
+    meta.reserve((size_t)meta_cap);
+    jobs.reserve((size_t)njobs_cap);
+    const uint64_t d_meta = (uint64_t)(uintptr_t)(d8 + o_meta);
+    const uint64_t d_scratch = (uint64_t)(uintptr_t)(d8 + o_scratch);
+    const uint64_t d_compact = (uint64_t)(uintptr_t)(d8 + o_compact);
+    for (int64_t i = f0; i < f1; i++) {
+      const FramePlan& fp = plan[(size_t)(i - f0)];
+      const zh_be::Layout& L = fp.L;
+      const size_t n = (size_t)frames[i].nbytes;
+      size_t total = 16 + 4 * (size_t)L.nblocks;
+      for (int64_t q = 0; q < fp.nstreams; q++) total += 4 + (size_t)cs[(size_t)(fp.first_stream + q)];
+      const bool memcpyed = n == 0 || fp.raw_only || total > n + 16;
+      const size_t cbytes = memcpyed ? n + 16 : total;
+      const size_t m0 = meta.size();
+      meta.resize(m0 + 16 + (memcpyed ? 0 : 4 * (size_t)L.nblocks));
+      zh_be::put_header(meta.data() + m0, L, memcpyed ? zh_be::memcpyed_flags(L) : L.flags, n,
+                        cbytes);
+      const uint64_t fbase = d_compact + (uint64_t)cpos;
+      jobs.push_back({d_meta + m0, fbase, (uint32_t)(meta.size() - m0), 0, 0, 0});
+      if (memcpyed) {
+        for (size_t o = 0; o < n; o += kJobBytes)
+          jobs.push_back({(uint64_t)(uintptr_t)frames[i].src + o, fbase + 16 + o,
+                          (uint32_t)std::min<size_t>(kJobBytes, n - o), 0, 0, 0});
+      } else {
+        size_t p = 16 + 4 * (size_t)L.nblocks;
+        for (uint32_t k = 0; k < L.nblocks; k++) {
+          const EncBlock& b = blocks[(size_t)fp.first_block + k];
+          zh_be::wr32(meta.data() + m0 + 16 + 4 * (size_t)k, (uint32_t)p);
+          const uint32_t neb = b.size / b.nstreams;
+          for (uint32_t q = 0; q < b.nstreams; q++) {
+            const uint32_t c = cs[b.first_stream + q];
+            jobs.push_back({d_scratch + b.scratch + (uint64_t)q * neb, fbase + p, c, c, 1, 0});
+            p += 4 + (size_t)c;
+          }
+        }
+      }
+      frames[i].dst_off = *pos + cpos;
+      frames[i].cbytes = (int64_t)cbytes;
+      frames[i].status = ZH_OK;
+      cpos += up((int64_t)cbytes, 16);
+    }
+    if ((int64_t)jobs.size() > njobs_cap || (int64_t)meta.size() > meta_cap || cpos > compact_cap)
+      rc = ZH_EHIP;  // the bounds above are the allocation
+  }
+  if (rc == ZH_OK && !jobs.empty()) {
+    if (!ring.h2d(d8 + o_jobs, (const uint8_t*)jobs.data(), jobs.size() * sizeof(GatherJob)) ||
+        !ring.h2d(d8 + o_meta, meta.data(), meta.size()))
+      rc = ZH_EHIP;
+    if (rc == ZH_OK) {
+      if (timed) (void)hipEventRecord(ev[2], s);
+      hipLaunchKernelGGL(blosc_gather_kernel, dim3((unsigned)jobs.size()), dim3(kThreads), 0, s,
+                         (const GatherJob*)(d8 + o_jobs));
+      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
+      if (timed) (void)hipEventRecord(ev[3], s);
+    }
+    if (rc == ZH_OK && !ring.d2h(dst + *pos, d8 + o_compact, (size_t)cpos)) rc = ZH_EHIP;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
+  if (rc == ZH_OK && timed && !jobs.empty()) {
+    float a = 0, b = 0;
+    if (!blocks.empty() && hipEventElapsedTime(&a, ev[0], ev[1]) != hipSuccess) a = 0;
+    if (hipEventElapsedTime(&b, ev[2], ev[3]) != hipSuccess) b = 0;
+    *kernel_ms += (double)a + (double)b;
+  }
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  zh::ctx_release(ctx, dmem, got);
+  if (rc == ZH_OK) *pos += cpos;
+  return rc;
+}
+
+int64_t bound_of(const zh_blosc_enc_frame* frames, int64_t n, const zh_blosc_enc_params* prm) {
+  if (n < 0 || (n > 0 && !frames)) return -(int64_t)ZH_EINVAL;
+  int64_t total = 0;
+  for (int64_t i = 0; i < n; i++) {
+    zh_be::Layout L;
+    if (frames[i].nbytes < 0 || zh_be::make_layout((size_t)frames[i].nbytes, prm, &L) != ZH_OK ||
+        (frames[i].nbytes > 0 && !frames[i].src))
+      return -(int64_t)ZH_EINVAL;
+    total += up(frames[i].nbytes + 16, 16);
+  }
+  return total;
+}
+
+constexpr const char* kBadParams =
+    "blosc encode: typesize 1..255, shuffle 0..2, blocksize >= 0, frames of at most 2 GiB";
+
+}  // namespace
+
+extern "C" {
+
+int zh_blosc_compress(const void* src, size_t n, const zh_blosc_enc_params* params, void* dst,
+                      size_t cap, size_t* cbytes, char* err, size_t errlen) {
+  size_t cb = 0;
+  const char* msg = "";
+  const int st = zh_be::compress_frame((const uint8_t*)src, n, params, (uint8_t*)dst, cap, &cb,
+                                       &msg);
+  if (st != ZH_OK) {
+    put_err(err, errlen, msg);
+    return st;
+  }
+  if (cbytes) *cbytes = cb;
+  return ZH_OK;
+}
+
+int64_t zh_blosc_encode_bound(const zh_blosc_enc_frame* frames, int64_t n,
+                              const zh_blosc_enc_params* params) {
+  return bound_of(frames, n, params);
+}
+
+double zh_debug_blosc_encode_kernel_ms(void) { return g_last_enc_ms.load(); }
+
+int zh_blosc_encode_batch(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
+                          const zh_blosc_enc_params* params, void* dst, int64_t dstcap,
+                          void* stream_v, char* err, size_t errlen) {
+  if (!ctx) return ZH_EINVAL;
+  const int64_t bound = bound_of(frames, n, params);
+  if (bound < 0) {
+    for (int64_t i = 0; i < n && frames; i++) frames[i].status = ZH_EINVAL;
+    put_err(err, errlen, kBadParams);
+    return ZH_EINVAL;
+  }
+  if (bound > dstcap || (bound > 0 && !dst)) {
+    put_err(err, errlen, "zh_blosc_encode_batch: destination smaller than zh_blosc_encode_bound");
+    return ZH_EINVAL;
+  }
+  if (n == 0) return ZH_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = stream_v ? (hipStream_t)stream_v : ctx->stream;
+  Ring ring;
+  int rc = ring.init(ctx, s);
+  int64_t pos = 0;
+  double ms = 0;
+  for (int64_t f0 = 0; f0 < n && rc == ZH_OK;) {
+    int64_t f1 = f0, raw = 0;
+    do raw += frames[f1++].nbytes;
+    while (f1 < n && raw + frames[f1].nbytes <= kSlabBytes);
+    rc = encode_slab(ctx, s, ring, frames, f0, f1, params, (uint8_t*)dst, &pos, &ms);
+    f0 = f1;
+  }
+  if (rc != ZH_OK) {
+    (void)hipGetLastError();
+    put_err(err, errlen, rc == ZH_ENOMEM ? "zh_blosc_encode_batch: out of device memory"
+                                         : "zh_blosc_encode_batch: device copy or launch failed");
+    return rc;
+  }
+  g_last_enc_ms.store(ms);
+  return ZH_OK;
+}
+
+}  // extern "C"

@@ -92,6 +92,17 @@ class zh_blosc_frame(C.Structure):
                 ("nbytes", C.c_int64), ("where", C.c_int32), ("status", C.c_int32)]
 
 
+class zh_blosc_enc_params(C.Structure):
+    """How blosc1 LZ4 frames are written (zarrhip.h zh_blosc_enc_params)."""
+    _fields_ = [("typesize", C.c_int32), ("shuffle", C.c_int32), ("blocksize", C.c_int32)]
+
+
+class zh_blosc_enc_frame(C.Structure):
+    """One frame of a batched device encode (zarrhip.h zh_blosc_enc_frame)."""
+    _fields_ = [("src", C.c_void_p), ("nbytes", C.c_int64), ("dst_off", C.c_int64),
+                ("cbytes", C.c_int64), ("status", C.c_int32)]
+
+
 class zh_file_store(C.Structure):
     """A FilesystemStore as the file reads name it (zarrhip.h zh_file_store)."""
     _fields_ = [("root", C.c_char_p), ("name", C.c_char_p)]

@@ -97,6 +97,13 @@ _SIGS = {
     "zh_blosc_decode_batch": (C.c_int, [P, C.POINTER(A.zh_blosc_frame), I64, P, I64, P, CH, SZ]),
     "zh_debug_blosc_kernel_ms": (C.c_double, []),
     "zh_debug_blosc_streams": (I64, [P, SZ, PI64, I64, CH, SZ]),
+    "zh_blosc_compress": (C.c_int, [P, SZ, C.POINTER(A.zh_blosc_enc_params), P, SZ,
+                                    C.POINTER(SZ), CH, SZ]),
+    "zh_blosc_encode_bound": (I64, [C.POINTER(A.zh_blosc_enc_frame), I64,
+                                    C.POINTER(A.zh_blosc_enc_params)]),
+    "zh_blosc_encode_batch": (C.c_int, [P, C.POINTER(A.zh_blosc_enc_frame), I64,
+                                        C.POINTER(A.zh_blosc_enc_params), P, I64, P, CH, SZ]),
+    "zh_debug_blosc_encode_kernel_ms": (C.c_double, []),
     "zh_zstd_decompress": (C.c_int, [P, SZ, P, SZ, C.POINTER(SZ), C.c_char_p, SZ]),
     "zh_zstd_compress_raw": (C.c_int, [P, SZ, C.c_int, P, SZ, C.POINTER(SZ)]),
     "zh_xxh64": (U64, [P, SZ, U64]),
@@ -436,6 +443,35 @@ class DeviceContext:
         del keep
         return ptr, [(arr[i].dst_off, arr[i].nbytes, arr[i].where) for i in range(len(frames))]
 
+    def blosc_encode_batch_raw(self, sources, typesize, shuffle, blocksize=0, stream=None,
+                               take=None):
+        """zh_blosc_encode_bound + zh_blosc_encode_batch over (device address, nbytes) pairs:
+        (the host buffer the frames arrived in, [(dst_off, cbytes)] per source).  `take(n)`: a
+        uint8 array of n bytes to receive them (default: a fresh one)."""
+        import numpy as np
+        n = len(sources)
+        arr = (A.zh_blosc_enc_frame * max(1, n))()
+        for i, (addr, nb) in enumerate(sources):
+            arr[i].src, arr[i].nbytes = addr, int(nb)
+        prm = A.zh_blosc_enc_params(int(typesize), int(shuffle), int(blocksize))
+        bound = self.L.zh_blosc_encode_bound(arr, n, C.byref(prm))
+        if bound < 0:
+            raise ZhError(int(-bound), "blosc encode: typesize 1..255, shuffle 0..2, "
+                                       "blocksize >= 0, frames of at most 2 GiB")
+        out = (take or (lambda k: np.empty(k, np.uint8)))(max(1, bound))
+        err = C.create_string_buffer(1024)
+        check(self.L.zh_blosc_encode_batch(self.h, arr, n, C.byref(prm), P(out.ctypes.data),
+                                           bound, P(stream), err, 1024), err)
+        return out, [(int(arr[i].dst_off), int(arr[i].cbytes)) for i in range(n)]
+
+    def blosc_encode_batch(self, sources, typesize, shuffle, blocksize=0, stream=None,
+                           take=None):
+        """The blosc1 LZ4 frames of (device address, nbytes) sources as a list of bytes."""
+        out, rows = self.blosc_encode_batch_raw(sources, typesize, shuffle, blocksize, stream,
+                                                take)
+        mv = memoryview(out)
+        return [bytes(mv[o:o + n]) for o, n in rows]
+
     def host_staging(self, nbytes):
         """zh_host_staging: the context's page-locked staging (valid until the next call)."""
         p = P()
@@ -589,6 +625,20 @@ def blosc_batch_plan(frames):
         check(int(-total), err)
     return int(total), [(arr[i].dst_off, arr[i].nbytes, arr[i].where)
                         for i in range(len(frames))]
+
+
+def blosc_compress(data, typesize, shuffle, blocksize=0):
+    """zh_blosc_compress (no device): one blosc1 LZ4 frame of `data` (shuffle 0 none, 1 byte,
+    2 bit)."""
+    L = lib()
+    data = bytes(data)
+    prm = A.zh_blosc_enc_params(int(typesize), int(shuffle), int(blocksize))
+    err = C.create_string_buffer(1024)
+    out = C.create_string_buffer(len(data) + 16)
+    n = C.c_size_t()
+    check(L.zh_blosc_compress(data, len(data), C.byref(prm), out, len(data) + 16, C.byref(n), err,
+                              1024), err)
+    return out.raw[:n.value]
 
 
 def blosc_streams(frame):

@@ -11,7 +11,8 @@ chunk codec work done by the HIP path through the C-ABI (libzarrhip.so).
 Byte-to-byte compressors stay on the host (north star): their frames are decoded here and
 the raw chunk bytes are handed to the device — except blosc frames, which
 one batched call decodes on the device when blosc is the chain's only host stage
-(ZH_BLOSC_DEVICE, zh_blosc_decode_batch).
+(ZH_BLOSC_DEVICE, zh_blosc_decode_batch), and blosc LZ4 frames, which Array.write compresses on
+the device (ZH_BLOSC_ENCODE_DEVICE, zh_blosc_encode_batch).
 """
 import atexit
 import ctypes as C
@@ -36,6 +37,11 @@ _ctx_lock = threading.Lock()
 # device in one batch (zh_blosc_decode_batch) instead of decoding them here one at a time.
 # The default follows the measurement in DESIGN.md ("Blosc frames on the device").
 BLOSC_DEVICE_DEFAULT = "1"
+# ZH_BLOSC_ENCODE_DEVICE: Array.write compresses a blosc LZ4 chain's frames on the device in one
+# batch (zh_blosc_encode_batch) instead of copying every raw chunk back and compressing it here.
+# It stays "1" whatever the write times say: the stored size is what the codec was asked for,
+# and both routes store the same bytes (DESIGN.md "Blosc frames encoded on the device").
+BLOSC_ENCODE_DEVICE_DEFAULT = "1"
 
 
 class _Deferred:
@@ -280,7 +286,7 @@ class Array:
             n *= c // i
         return n
 
-    def _wrap_inner(self, shard):
+    def _wrap_inner(self, shard, info=None):
         """Inverse of _unwrap_inner for the write path."""
         ch = self.chain.chain
         n_in = self._n_inner()
@@ -297,7 +303,9 @@ class Array:
             if off == 2 ** 64 - 1:
                 new.append((off, nb))
                 continue
-            enc = host_bb_encode(self.chain.inner_host_bb, shard[off:off + nb])
+            if info is not None:
+                info["raw_bytes"] += nb
+            enc = self._bb_encode(self.chain.inner_host_bb, shard[off:off + nb], info)
             new.append((pos, len(enc)))
             payload.append(enc)
             pos += len(enc)
@@ -741,15 +749,19 @@ class Array:
         paths = None if keep_fill else self._file_paths(coords, [dev])
         if paths is not None:  # the library writes (and deletes) the chunk files itself
             try:
-                dev.array_write_files(self.zmeta, data.ctypes.data, offset, shape, paths,
-                                      store=self._file_store())
+                sizes = dev.array_write_files(self.zmeta, data.ctypes.data, offset, shape, paths,
+                                              store=self._file_store())
             except _lib.ZhError as e:
                 raise_for(e)
+            self.last_write_info = {"blosc_device_frames": 0, "blosc_host_frames": 0,
+                                    "raw_bytes": sum(sizes), "stored_bytes": sum(sizes)}
             return
         L = _lib.lib()
         cap = L.zh_array_encoded_bound(C.byref(self.zmeta))
         src = dev.malloc(max(1, data.nbytes))
         bufs = []
+        info = {"blosc_device_frames": 0, "blosc_host_frames": 0, "raw_bytes": 0,
+                "stored_bytes": 0}
         try:
             dev.memcpy(src, data.ctypes.data, data.nbytes, 0)
             bufs = [dev.malloc(cap) for _ in coords]
@@ -757,10 +769,16 @@ class Array:
                 sizes = dev.array_write(self.zmeta, src, offset, shape, [(b, cap) for b in bufs])
             except _lib.ZhError as e:
                 raise_for(e)
-            for c, b, sz in zip(coords, bufs, sizes):
+            stored = self._blosc_frames_device(dev, bufs, sizes, info) \
+                if self._blosc_encode_device() else {}
+            for k, (c, b, sz) in enumerate(zip(coords, bufs, sizes)):
                 h = self._handle(c)
                 if sz == 0 and not keep_fill:
                     h.delete()  # all fill → writeChunk deletes the key (Array.java:150-151)
+                    continue
+                if k in stored:  # its frames were made on the device
+                    info["stored_bytes"] += len(stored[k])
+                    h.set(stored[k])
                     continue
                 if sz == 0:
                     # no fill value (v2 "fill_value": null): writeChunk never deletes
@@ -771,14 +789,97 @@ class Array:
                 else:
                     enc = dev.d2h(b, sz)
                 if self.chain.host_bb:
-                    enc = host_bb_encode(self.chain.host_bb, enc)
+                    info["raw_bytes"] += len(enc)
+                    enc = self._bb_encode(self.chain.host_bb, enc, info)
                 elif self.chain.inner_host_bb:
-                    enc = self._wrap_inner(enc)
+                    enc = self._wrap_inner(enc, info)
+                else:
+                    info["raw_bytes"] += len(enc)
+                info["stored_bytes"] += len(enc)
                 h.set(enc)
         finally:
             for b in bufs:
                 dev.free(b)
             dev.free(src)
+        self.last_write_info = info
+
+    def _bb_encode(self, bb, enc, info=None):
+        """host_bb_encode; a blosc chain's codec gets the dtype's byte count for an unset
+        typesize, as the device route passes it down."""
+        if self._blosc_chain():
+            if info is not None:
+                info["blosc_host_frames"] += 1
+            return bb[0].encode(enc, self.metadata.data_type.getByteCount())
+        return host_bb_encode(bb, enc)
+
+    def _blosc_encode_device(self):
+        """Array.write makes the chain's blosc frames on the device (zh_blosc_encode_batch):
+        blosc is the only host byte-to-byte stage, its cname is lz4 / lz4hc (the one blosc
+        compressor written here; clevel is not honoured), one device is in use and
+        ZH_BLOSC_ENCODE_DEVICE is not "0"."""
+        if not self._blosc_chain() or len(devices()) != 1 or \
+                os.environ.get("ZH_BLOSC_ENCODE_DEVICE", BLOSC_ENCODE_DEVICE_DEFAULT) == "0":
+            return False
+        bb = self.chain.inner_host_bb if self.chain.chain["sharded"] else self.chain.host_bb
+        return bb[0].lz4()
+
+    def _blosc_frames_device(self, dev, bufs, sizes, info):
+        """The stored objects of the chunks with sz > 0, their blosc frames compressed on the
+        device in one batch over the chunk buffers: {chunk number: bytes}.  Unsharded: the
+        chunk is one frame.  Sharded: only the stored index comes back as it is; every present
+        entry is one frame, and the shard is put together as _wrap_inner does."""
+        ch = self.chain.chain
+        sharded = ch["sharded"]
+        codec = (self.chain.inner_host_bb if sharded else self.chain.host_bb)[0]
+        ts, shuffle, blocksize = codec.enc_params(self.metadata.data_type.getByteCount())
+        sources, shards = [], {}
+        if sharded:
+            n_in = self._n_inner()
+            isz = _lib.lib().zh_shard_index_size(C.byref(self.zmeta))
+            start = ch["index_location"] == A.ZH_INDEX_START
+            fmt = ">QQ" if ch["index_endian"] == A.ZH_ENDIAN_BIG else "<QQ"
+        for k, (b, sz) in enumerate(zip(bufs, sizes)):
+            if sz == 0:
+                continue
+            if not sharded:
+                sources.append((b, sz))
+                continue
+            idx = dev.d2h(b + (0 if start else sz - isz), isz)
+            ents = [struct.unpack(fmt, idx[16 * e:16 * e + 16]) for e in range(n_in)]
+            shards[k] = ents
+            sources.extend((b + off, nb) for off, nb in ents if off != 2 ** 64 - 1)
+        lease = []  # the frames land in a pooled buffer: no fresh pages per write
+        try:
+            frames = dev.blosc_encode_batch(sources, ts, shuffle, blocksize,
+                                            take=lambda n: staging_pool.take(n, lease))
+        except _lib.ZhError as e:
+            if e.status == A.ZH_EINVAL:
+                raise ZarrException(f"Error in encoding blosc: {e}") from None
+            raise_for(e)
+        finally:
+            staging_pool.give(lease)
+        info["blosc_device_frames"] += len(frames)
+        info["raw_bytes"] += sum(nb for _, nb in sources)
+        if not sharded:
+            return dict(zip([k for k, sz in enumerate(sizes) if sz > 0], frames))
+        it, out = iter(frames), {}
+        for k, ents in shards.items():
+            pos = isz if start else 0
+            payload, new = [], []
+            for off, nb in ents:
+                if off == 2 ** 64 - 1:
+                    new.append((off, nb))
+                    continue
+                f = next(it)
+                new.append((pos, len(f)))
+                payload.append(f)
+                pos += len(f)
+            ib = b"".join(struct.pack(fmt, *e) for e in new)
+            if ch["index_crc32c"]:
+                ib = self.chain.index_codecs[1].encode(ib)
+            pb = b"".join(payload)
+            out[k] = ib + pb if start else pb + ib
+        return out
 
     def access(self):
         return ArrayAccessor(self)

@@ -259,8 +259,12 @@ class GzipCodec(Codec):
 class BloscCodec(Codec):
     """BloscCodec (M/v3/codec/core/BloscCodec.java) — host only.  Frames are decoded by
     zh_blosc_decompress (BloscLZ / LZ4 / zlib / zstd payloads, byte and bit shuffle; snappy
-    raises UnsupportedChainError); encode writes MEMCPYED frames (no compressor here)."""
+    raises UnsupportedChainError).  encode compresses cname lz4 / lz4hc with the library's own
+    LZ4 writer (zh_blosc_compress: byte-identical to the frames Array.write makes on the
+    device; clevel is not honoured, and blocks are at most 64 KiB); every other cname is
+    written as a MEMCPYED frame (no compressor for it here)."""
     name, kind = "blosc", "bb"
+    SHUFFLE_CODE = {"noshuffle": 0, "shuffle": 1, "bitshuffle": 2}
 
     def __init__(self, cname="zstd", clevel=5, shuffle="noshuffle", typesize=None, blocksize=0):
         self.cfg = {"typesize": typesize, "cname": cname, "clevel": clevel, "shuffle": shuffle,
@@ -284,8 +288,23 @@ class BloscCodec(Codec):
             raise ZarrException(f"Error in decoding blosc: {err.value.decode()}")
         return bytes(out)[:n.value]
 
-    def encode(self, b):
+    def lz4(self):
+        return self.cfg.get("cname") in ("lz4", "lz4hc")
+
+    def enc_params(self, default_typesize=1):
+        """(typesize, shuffle code, blocksize) as zh_blosc_enc_params takes them."""
+        return (self.cfg.get("typesize") or default_typesize,
+                self.SHUFFLE_CODE[self.cfg.get("shuffle") or "noshuffle"],
+                int(self.cfg.get("blocksize") or 0))
+
+    def encode(self, b, default_typesize=1):
         b = bytes(b)
+        if self.lz4():
+            from ._lib import ZhError, blosc_compress
+            try:
+                return blosc_compress(b, *self.enc_params(default_typesize))
+            except ZhError as e:
+                raise ZarrException(f"Error in encoding blosc: {e}") from None
         ts = self.cfg.get("typesize") or 1
         hdr = struct.pack("<BBBBIII", 2, 1, 0x02 | 0x01, ts, len(b), len(b), len(b) + 16)
         return hdr + b
