@@ -691,6 +691,53 @@ int zh_zstd_compress_raw(const void* src, size_t srclen, int checksum, void* dst
                          size_t* dstlen);
 uint64_t zh_xxh64(const void* data, size_t len, uint64_t seed);
 
+/* ---- zstd frames written by the library, on the host or on the device ---------------
+ * One frame per call / per source, never concatenated frames.  The content is cut into blocks
+ * of `blocksize` bytes, each compressed on its own (greedy LZ over a 1024-slot table, raw
+ * literals, sequences FSE-coded with the predefined tables, no repeat offsets); a block that
+ * would not shrink is a raw block, neighbouring raw blocks are merged up to 128 KiB, and a frame
+ * that would reach the size of zh_zstd_compress_raw's is written as that frame, byte for byte.
+ * The bytes are a pure function of (input, block size, checksum): the host call and the batch
+ * call give the same frame.  The codec's `level` is not honoured. */
+typedef struct zh_zstd_enc_params {
+  int32_t checksum;   /* 0 / 1: the XXH64 content checksum                              */
+  int32_t blocksize;  /* 0: default (16 KiB); below 1 KiB: 1 KiB; above 64 KiB: 64 KiB  */
+} zh_zstd_enc_params;
+
+typedef struct zh_zstd_enc_frame {
+  const void* src;   /* raw bytes: device memory                               */
+  int64_t nbytes;
+  int64_t dst_off;   /* out: place of the frame in dst, 16-byte aligned        */
+  int64_t cbytes;    /* out: size of the frame                                 */
+  int32_t status;    /* out: ZH_OK or this frame's error                       */
+} zh_zstd_enc_frame;
+
+/* Host, no device: one frame.  dst == NULL: *len = the bound, the size of the raw-block frame
+ * (cap must reach it otherwise). */
+int zh_zstd_compress(const void* src, size_t n, const zh_zstd_enc_params* params, void* dst,
+                     size_t cap, size_t* len, char* err, size_t errlen);
+
+/* Host memory a batch needs for its frames: the sum of the bounds, each rounded up to 16
+ * bytes; or -zh_status. */
+int64_t zh_zstd_encode_bound(const zh_zstd_enc_frame* frames, int64_t n,
+                             const zh_zstd_enc_params* params);
+
+/* Sources in device memory; the frames arrive in host memory dst (dstcap >= the bound) at
+ * dst_off, cbytes long.  One kernel matches (one wavefront per block), a second codes the
+ * sequences (one thread per block), a third hashes the content (one wavefront per frame), a
+ * fourth lays the frames out; they leave through the context's page-locked ring.  Runs on
+ * `stream` (NULL: the context's) and waits.  Slabs of at most 128 MiB of raw bytes (a larger
+ * frame is its own slab) bound the device memory of a call. */
+int zh_zstd_encode_batch(zh_ctx* ctx, zh_zstd_enc_frame* frames, int64_t n,
+                         const zh_zstd_enc_params* params, void* dst, int64_t dstcap,
+                         void* stream, char* err, size_t errlen);
+
+/* Diagnostics: milliseconds the kernels of the last successful zh_zstd_encode_batch took, by
+ * device events, summed over its slabs (-1: none yet); XXH64 (seed 0) of n device buffers by
+ * the batch's hash kernel into out[n] (host). */
+double zh_debug_zstd_encode_kernel_ms(void);
+int zh_debug_zstd_xxh64(zh_ctx* ctx, const zh_zstd_enc_frame* frames, int64_t n, uint64_t* out);
+
 /* dst block b ← src block src_block[b] (device buffers, blocks of block_bytes, a multiple of
  * 16; 16-byte aligned; src_block on the host), synchronous: re-lays out encoded shards, e.g.
  * the bench's shuffled inner-chunk order. */

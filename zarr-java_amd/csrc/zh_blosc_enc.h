@@ -7,25 +7,11 @@
 //   * make_layout: block size, split rule and flags of a frame of n bytes;
 //   * shuffled_byte_at: byte o of the shuffled block, read from the raw block (the inverse of
 //     zh_bs::unshuffle_byte_at);
-//   * encode_stream: one stream (s, n) -> LZ4 bytes, written once over a lane policy W.  The
-//     algorithm is stated for the 64 lanes of a wave: at cursor p lane l looks at p + l, hashes
-//     4 bytes, reads its candidate from the table, checks the 4 bytes (failing that, the 4
-//     bytes one position back: a run, which the table cannot know inside one step); the lowest
-//     matching lane wins, the match is extended 64 bytes per step, the sequence is written, the
-//     table takes the positions before the new cursor, the cursor moves behind the match.
-//     Lookups of one step see the table as the previous step left it, and two lanes that hash
-//     to one slot
-//     resolve by maximum (the slot keeps the highest position + 1), so the output is a pure
-//     function of (input bytes, n).  W:
-//         void     clear(uint32_t* table)
-//         uint32_t find(s, p, lim, table, &ref)   lowest lane whose candidate matches (64: none);
-//                                                 keeps every lane's hash for insert
-//         void     insert(p, end, table)          table[hash] = max(., q + 1) for p <= q < end
-//         uint32_t extend(s, a, b, maxn)          leading k < maxn with s[a + k] == s[b + k]
-//         void     copy(d, s, n)  /  lenbytes(d, v)  /  put(d, byte)
-//     HostLanes loops over the 64 lane indices; the kernel's WaveLanes (zh_blosc_enc_kernels.hip)
-//     is one wave.  A stream whose encoding would reach its raw size returns n before writing
-//     past out[n - 1]: the caller stores it raw;
+//   * encode_stream: one stream (s, n) -> LZ4 bytes, written once over a lane policy W: the
+//     match finder, its determinism rule and the policy's members are stated in zh_lz_match.h
+//     (HostLanes there, the kernel's WaveLanes in zh_enc_device.h), so the output is a pure
+//     function of (input bytes, n).  A stream whose encoding would reach its raw size returns
+//     n before writing past out[n - 1]: the caller stores it raw;
 //   * compress_frame: the whole frame on the host with HostLanes (zh_blosc_compress, the
 //     kernel's byte-for-byte oracle, tools/blosc_enc_check.cpp under sanitizers).
 // LZ4 end rules (liblz4 decodes the streams): the last 5 bytes are literals, no match starts
@@ -37,13 +23,19 @@
 #include <stdint.h>
 
 #include "zh_blosc_streams.h"
+#include "zh_lz_match.h"
 
 namespace zh_be {
 
-constexpr uint32_t kMaxBlock = 64u << 10;      // kLdsBlock of the decoder: blocks stay in LDS
+// the match finder and its host lane policy: zh_lz_match.h, shared with the zstd writer
+using zh_lz::HostLanes;
+using zh_lz::hash4;
+using zh_lz::kHashBits;
+using zh_lz::kHashSize;
+using zh_lz::kMaxBlock;  // kLdsBlock of the decoder: blocks stay in LDS
+using zh_lz::ld32;
+
 constexpr uint32_t kDefaultBlock = 16u << 10;  // DESIGN.md "Blosc frames encoded on the device"
-constexpr uint32_t kHashBits = 10;
-constexpr uint32_t kHashSize = 1u << kHashBits;  // uint32 slots per wave: position + 1, 0 empty
 constexpr size_t kMaxFrame = 0x7fffffffu - 16;   // blosc1: nbytes + 16 fits an int32
 
 struct Layout {
@@ -99,58 +91,8 @@ ZH_BS_HD uint8_t shuffled_byte_at(const uint8_t* in, uint32_t o, uint32_t size, 
   return in[o];
 }
 
-ZH_BS_HD uint32_t ld32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-ZH_BS_HD uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - kHashBits); }
 // bytes a length beyond the token's 4 bits takes (0 below 15)
 ZH_BS_HD uint32_t len_extra(uint32_t v) { return v >= 15 ? (v - 15) / 255 + 1 : 0; }
-
-// The 64 lanes as a loop: the host form of the lane policy.
-struct HostLanes {
-  uint32_t h[64];
-  void clear(uint32_t* table) {
-    for (uint32_t i = 0; i < kHashSize; i++) table[i] = 0;
-  }
-  uint32_t find(const uint8_t* s, uint32_t p, uint32_t lim, const uint32_t* table,
-                uint32_t* ref) {
-    uint32_t best = 64;
-    for (uint32_t l = 0; l < 64; l++) {
-      const uint32_t q = p + l;
-      if (q > lim) break;
-      const uint32_t v = ld32(s + q);
-      h[l] = hash4(v);
-      const uint32_t c = table[h[l]];
-      if (best != 64) continue;
-      if (c != 0 && ld32(s + c - 1) == v) {
-        best = l;
-        *ref = c - 1;
-      } else if (q >= 1 && ld32(s + q - 1) == v) {  // a run: the table only knows earlier steps
-        best = l;
-        *ref = q - 1;
-      }
-    }
-    return best;
-  }
-  void insert(uint32_t p, uint32_t end, uint32_t* table) {
-    for (uint32_t l = 0; l < 64 && p + l < end; l++)
-      if (table[h[l]] < p + l + 1) table[h[l]] = p + l + 1;
-  }
-  uint32_t extend(const uint8_t* s, uint32_t a, uint32_t b, uint32_t maxn) {
-    uint32_t k = 0;
-    while (k < maxn && s[a + k] == s[b + k]) k++;
-    return k;
-  }
-  void copy(uint8_t* d, const uint8_t* s, uint32_t n) {
-    for (uint32_t k = 0; k < n; k++) d[k] = s[k];
-  }
-  void lenbytes(uint8_t* d, uint32_t v) {
-    const uint32_t nfull = v / 255;
-    for (uint32_t k = 0; k < nfull; k++) d[k] = 255;
-    d[nfull] = (uint8_t)(v % 255);
-  }
-  void put(uint8_t* d, uint32_t b) { *d = (uint8_t)b; }
-};
 
 // One LZ4 sequence at out + o: token, literal length, literals, then (ml != 0) offset and match
 // length.  The caller has checked the room.

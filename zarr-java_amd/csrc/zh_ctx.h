@@ -60,6 +60,9 @@ struct zh_ctx {
   // the D2H goes here as a DMA and one memcpy moves it out; used under mu, created on first use
   uint8_t* hout_pin = nullptr;
   bool hout_pin_failed = false;
+  // the zstd writer's encoding tables (zh_ze::Tables) in device memory, uploaded on first use
+  // under mu (zh_zstd_enc_kernels.hip)
+  void* zstd_tables = nullptr;
 };
 
 namespace zh {

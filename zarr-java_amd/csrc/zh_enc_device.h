@@ -1,0 +1,202 @@
+// zh_enc_device.h — what the device frame writers share (zh_blosc_enc_kernels.hip,
+// zh_zstd_enc_kernels.hip): the wave form of the lane policy of zh_lz_match.h, the gather kernel
+// that lays finished pieces out as compact frames, and the copies through the context's
+// page-locked rings.  Device code: included by .hip files only, each of which gets its own copy
+// (anonymous namespace).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "zh_ctx.h"
+#include "zh_lz_match.h"
+
+namespace {
+
+constexpr int kWaves = 4;
+constexpr int kThreads = kWaves * 64;
+
+// One copy of the gather kernel: an optional word of 1..4 bytes (a blosc csize, a zstd block
+// header), then n bytes.
+struct GatherJob {
+  uint64_t src, dst;  // device addresses
+  uint32_t n, word, wbytes, pad;  // wbytes (0..4) low bytes of word go before the n bytes
+};
+
+
+// The lane policy of zh_lz_match.h for one wave.
+struct WaveLanes {
+  uint32_t lane, h;
+  bool wide = false;  // as HostLanes::wide
+
+  // Between two steps only the table in LDS is read by other lanes than wrote it: the wave
+  // waits for its LDS operations, never for its stores to the scratch (nothing reads those back).
+  __device__ static void order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+  // Before the raw copy overwrites what the abandoned encoding stored in the same region.
+  __device__ static void drain_stores() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __device__ void clear(uint32_t* table) {
+    for (uint32_t i = lane; i < zh_lz::kHashSize; i += 64) table[i] = 0;
+    order();
+  }
+  __device__ uint32_t find(const uint8_t* s, uint32_t p, uint32_t lim, const uint32_t* table,
+                           uint32_t* ref) {
+    const uint32_t q = p + lane;
+    uint32_t c = 0;
+    bool ok = false;
+    if (q <= lim) {
+      const uint32_t v = zh_lz::ld32(s + q);
+      h = zh_lz::hash4(v);
+      c = table[h];
+      ok = c != 0 && zh_lz::ld32(s + c - 1) == v;
+      if (!ok && q >= 1 && zh_lz::ld32(s + q - 1) == v) ok = true, c = q;  // a run
+      if (wide) {
+        for (uint32_t d = 2; d <= 8; d *= 2)
+          if (!ok && q >= d && zh_lz::ld32(s + q - d) == v) ok = true, c = q - d + 1;
+      }
+    }
+    const unsigned long long b = __ballot(ok);
+    if (!b) return 64;
+    const int first = __builtin_ctzll(b);
+    *ref = (uint32_t)__builtin_amdgcn_readlane((int)c, first) - 1;
+    return (uint32_t)first;
+  }
+  __device__ void insert(uint32_t p, uint32_t end, uint32_t* table) {
+    if (p + lane < end) atomicMax(&table[h], p + lane + 1);
+    order();
+  }
+  __device__ uint32_t extend(const uint8_t* s, uint32_t a, uint32_t b, uint32_t maxn) {
+    for (uint32_t k0 = 0; k0 < maxn; k0 += 64) {
+      const uint32_t k = k0 + lane;
+      const bool differ = k >= maxn || s[a + k] != s[b + k];
+      const unsigned long long m = __ballot(differ);
+      if (m) return k0 + (uint32_t)__builtin_ctzll(m);
+    }
+    return maxn;
+  }
+  __device__ void copy(uint8_t* d, const uint8_t* s, uint32_t n) {
+    for (uint32_t k = lane; k < n; k += 64) d[k] = s[k];
+  }
+  __device__ void lenbytes(uint8_t* d, uint32_t v) {
+    const uint32_t nfull = v / 255;
+    for (uint32_t k = lane; k <= nfull; k += 64) d[k] = k < nfull ? 255 : (uint8_t)(v % 255);
+  }
+  __device__ void put(uint8_t* d, uint32_t b) {
+    if (lane == 0) *d = (uint8_t)b;
+  }
+  __device__ void put16(uint16_t* d, uint32_t v) {
+    if (lane == 0) *d = (uint16_t)v;
+  }
+};
+
+__global__ __launch_bounds__(kThreads) void blosc_gather_kernel(
+    const GatherJob* __restrict__ jobs) {
+  const GatherJob j = jobs[blockIdx.x];
+  const uint8_t* s = (const uint8_t*)j.src;
+  uint8_t* d = (uint8_t*)j.dst;
+  const uint32_t t = threadIdx.x;
+  if (j.wbytes) {
+    if (t < j.wbytes) d[t] = (uint8_t)(j.word >> (8 * t));
+    d += j.wbytes;
+  }
+  uint32_t n = j.n;
+  uint32_t head = (uint32_t)((16 - (((uintptr_t)d) & 15)) & 15);
+  if (head > n) head = n;
+  if (t < head) d[t] = s[t];
+  s += head, d += head, n -= head;
+  const uint32_t nv = n / 16;
+  const uint32_t sh = (uint32_t)(((uintptr_t)s) & 3);
+  if ((((uintptr_t)s) & 15) == 0) {
+    for (uint32_t i = t; i < nv; i += kThreads) ((uint4*)d)[i] = ((const uint4*)s)[i];
+  } else {
+    // the source is not aligned with the destination: aligned words, shifted into place.  The
+    // fifth word holds at least one byte of the range when sh != 0, and is not read otherwise.
+    const uint32_t* s4 = (const uint32_t*)(s - sh);
+    for (uint32_t i = t; i < nv; i += kThreads) {
+      uint32_t x[5];
+      for (int k = 0; k < 4; k++) x[k] = s4[4 * i + k];
+      x[4] = sh ? s4[4 * i + 4] : 0u;
+      uint32_t y[4];
+      for (int k = 0; k < 4; k++) y[k] = sh ? __builtin_amdgcn_alignbyte(x[k + 1], x[k], sh) : x[k];
+      ((uint4*)d)[i] = make_uint4(y[0], y[1], y[2], y[3]);
+    }
+  }
+  for (uint32_t q = nv * 16 + t; q < n; q += kThreads) d[q] = s[q];
+}
+
+void put_err(char* err, size_t errlen, const char* msg) {
+  if (err && errlen) {
+    strncpy(err, msg, errlen - 1);
+    err[errlen - 1] = 0;
+  }
+}
+
+inline int64_t up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+// Through the context's page-locked rings, one slot at a time in flight per ring slot.
+struct Ring {
+  zh_ctx* ctx;
+  hipStream_t s;
+  size_t slot_bytes = 0;
+  std::vector<hipEvent_t> ev;
+
+  int init(zh_ctx* c, hipStream_t st) {
+    ctx = c, s = st;
+    int lanes;
+    int64_t window;
+    const int rc = zh::pipe_out_ring(ctx, &lanes, &window);
+    if (rc != ZH_OK) return rc;
+    slot_bytes = (size_t)window;
+    ev.assign(ctx->ring_out.size(), nullptr);
+    for (auto& e : ev)
+      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return ZH_EHIP;
+    return ev.empty() || slot_bytes == 0 ? ZH_EHIP : ZH_OK;
+  }
+  ~Ring() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  // device -> host memory, the copies pipelined over the out ring's slots; returns when done
+  bool d2h(uint8_t* h, const uint8_t* d, size_t n) {
+    const size_t nslots = ev.size(), nchunks = (n + slot_bytes - 1) / slot_bytes;
+    auto land = [&](size_t i) {
+      if (hipEventSynchronize(ev[i % nslots]) != hipSuccess) return false;
+      const size_t off = i * slot_bytes;
+      memcpy(h + off, ctx->ring_out[i % nslots], std::min(slot_bytes, n - off));
+      return true;
+    };
+    for (size_t i = 0; i < nchunks; i++) {
+      if (i >= nslots && !land(i - nslots)) return false;
+      const size_t off = i * slot_bytes;
+      if (hipMemcpyAsync(ctx->ring_out[i % nslots], d + off, std::min(slot_bytes, n - off),
+                         hipMemcpyDeviceToHost, s) != hipSuccess ||
+          hipEventRecord(ev[i % nslots], s) != hipSuccess)
+        return false;
+    }
+    for (size_t i = nchunks > nslots ? nchunks - nslots : 0; i < nchunks; i++)
+      if (!land(i)) return false;
+    return true;
+  }
+  // host tables -> device through the in ring (small: one slot, reused)
+  bool h2d(uint8_t* d, const uint8_t* h, size_t n) {
+    for (size_t off = 0; off < n; off += slot_bytes) {
+      const size_t take = std::min(slot_bytes, n - off);
+      memcpy(ctx->ring_in[0], h + off, take);
+      if (hipMemcpyAsync(d + off, ctx->ring_in[0], take, hipMemcpyHostToDevice, s) != hipSuccess ||
+          hipStreamSynchronize(s) != hipSuccess)
+        return false;
+    }
+    return true;
+  }
+};
+
+}  // namespace

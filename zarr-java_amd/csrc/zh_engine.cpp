@@ -296,6 +296,7 @@ void zh_ctx_destroy(zh_ctx* c) {
   if (c->file_pin) (void)hipHostFree(c->file_pin);
   if (c->hout_pin) (void)hipHostFree(c->hout_pin);
   if (c->wscratch) (void)hipFree(c->wscratch);
+  if (c->zstd_tables) (void)hipFree(c->zstd_tables);
   for (auto& kv : c->cache) (void)hipFree(kv.second);
   pipeline_release(c);
   delete c;

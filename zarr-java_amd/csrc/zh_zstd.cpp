@@ -9,9 +9,9 @@
 // blocks; raw / RLE / Huffman-compressed / treeless literals with 1 or 4 streams; Huffman trees
 // with direct or FSE-compressed weights; sequences with predefined / RLE / FSE / repeat tables;
 // repeat offsets; the optional XXH64 content checksum.  Dictionaries are not (zarr's zstd codec
-// has none): a frame naming one is rejected as unsupported.  The encoder side writes valid
-// frames of raw blocks (content size and, if asked, the checksum), which every zstd decoder
-// reads; it does not compress.
+// has none): a frame naming one is rejected as unsupported.  The encoder side: zh_zstd_compress
+// is the host form of the block writer of zh_zstd_enc.h, whose encoding tables are derived here
+// from the decoder's Fse::build; zh_zstd_compress_raw writes frames of raw blocks.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/zarrhip.h"
+#include "zh_zstd_enc.h"
 
 namespace {
 
@@ -362,6 +363,53 @@ const int16_t kMLDefault[53] = {1, 4, 3, 2, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 
 const int16_t kOFDefault[29] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1,
                                 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1};
 
+// ---- the encoder's view of the predefined tables ---------------------------------------
+// For a symbol s, the decode-table states carrying s partition the next-state range: state S
+// covers [base[S], base[S] + 2^nbits[S]).  So (s, next state) names one state.
+template <int NSYM, int SIZE>
+void fill_enc(const Fse& f, uint8_t (*state)[SIZE], uint8_t* first, uint8_t* nb, uint16_t* base) {
+  for (int s = 0; s < NSYM; s++) {
+    first[s] = 0xFF;
+    for (int n = 0; n < SIZE; n++) state[s][n] = 0xFF;
+  }
+  for (int S = 0; S < SIZE; S++) {
+    const int s = f.sym[S];
+    nb[S] = f.nbits[S];
+    base[S] = f.base[S];
+    if (first[s] == 0xFF) first[s] = (uint8_t)S;
+    for (int n = f.base[S]; n < f.base[S] + (1 << f.nbits[S]); n++) {
+      if (state[s][n] != 0xFF) fail("zstd: predefined table states overlap");
+      state[s][n] = (uint8_t)S;
+    }
+  }
+  for (int s = 0; s < NSYM; s++)
+    for (int n = 0; n < SIZE; n++)
+      if (state[s][n] == 0xFF) fail("zstd: predefined table leaves a next state uncovered");
+}
+
+zh_ze::Tables make_enc_tables() {
+  zh_ze::Tables T;
+  memset(&T, 0, sizeof T);
+  Fse ll, ml, of;
+  ll.build(kLLDefault, 36, 6);
+  ml.build(kMLDefault, 53, 6);
+  of.build(kOFDefault, 29, 5);
+  fill_enc<36, 64>(ll, T.ll_state, T.ll_first, T.ll_nb, T.ll_base);
+  fill_enc<53, 64>(ml, T.ml_state, T.ml_first, T.ml_nb, T.ml_base);
+  fill_enc<29, 32>(of, T.of_state, T.of_first, T.of_nb, T.of_base);
+  for (int c = 0; c < 36; c++) T.ll_cbase[c] = kLLBase[c], T.ll_cbits[c] = kLLBits[c];
+  for (int c = 0; c < 53; c++) T.ml_cbase[c] = kMLBase[c], T.ml_cbits[c] = kMLBits[c];
+  for (uint32_t v = 0, c = 0; v < 64; v++) {
+    while (c + 1 < 36 && kLLBase[c + 1] <= v) c++;
+    T.ll_code[v] = (uint8_t)c;
+  }
+  for (uint32_t v = 0, c = 0; v < 128; v++) {  // v = match length - 3
+    while (c + 1 < 53 && kMLBase[c + 1] <= v + 3) c++;
+    T.ml_code[v] = (uint8_t)c;
+  }
+  return T;
+}
+
 // ---- frame decoder -----------------------------------------------------------------------
 struct FrameState {
   Huf huf;
@@ -669,7 +717,30 @@ int run(const uint8_t* s, size_t n, Out& out, char* err, size_t errlen) {
 
 }  // namespace
 
+const zh_ze::Tables& zh_ze::tables() {
+  static const zh_ze::Tables T = make_enc_tables();
+  return T;
+}
+
 extern "C" {
+
+// One compressed frame on the host (zh_zstd_enc.h over HostLanes): the device batch's oracle.
+int zh_zstd_compress(const void* src, size_t n, const zh_zstd_enc_params* params, void* dst,
+                     size_t cap, size_t* len, char* err, size_t errlen) {
+  const char* msg = "";
+  try {
+    const int st = zh_ze::compress_frame(zh_ze::tables(), (const uint8_t*)src, n, params,
+                                         (uint8_t*)dst, cap, len, &msg);
+    if (st != ZH_OK) set_err(err, errlen, msg);
+    return st;
+  } catch (const Fail& f) {
+    set_err(err, errlen, f.msg);
+    return f.status;
+  } catch (const std::bad_alloc&) {
+    set_err(err, errlen, "zstd: out of memory");
+    return ZH_ENOMEM;
+  }
+}
 
 // Size query (dst == NULL): the sum of the frames' declared content sizes, or, when a frame
 // omits its size, a full decode pass without output.  Decode: dstcap must hold the content.

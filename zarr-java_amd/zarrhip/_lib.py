@@ -107,6 +107,14 @@ _SIGS = {
     "zh_zstd_decompress": (C.c_int, [P, SZ, P, SZ, C.POINTER(SZ), C.c_char_p, SZ]),
     "zh_zstd_compress_raw": (C.c_int, [P, SZ, C.c_int, P, SZ, C.POINTER(SZ)]),
     "zh_xxh64": (U64, [P, SZ, U64]),
+    "zh_zstd_compress": (C.c_int, [P, SZ, C.POINTER(A.zh_zstd_enc_params), P, SZ, C.POINTER(SZ),
+                                   CH, SZ]),
+    "zh_zstd_encode_bound": (I64, [C.POINTER(A.zh_zstd_enc_frame), I64,
+                                   C.POINTER(A.zh_zstd_enc_params)]),
+    "zh_zstd_encode_batch": (C.c_int, [P, C.POINTER(A.zh_zstd_enc_frame), I64,
+                                       C.POINTER(A.zh_zstd_enc_params), P, I64, P, CH, SZ]),
+    "zh_debug_zstd_encode_kernel_ms": (C.c_double, []),
+    "zh_debug_zstd_xxh64": (C.c_int, [P, C.POINTER(A.zh_zstd_enc_frame), I64, C.POINTER(U64)]),
     "zh_device_malloc": (C.c_int, [P, SZ, C.POINTER(P)]),
     "zh_device_malloc_ex": (C.c_int, [P, SZ, C.c_uint, C.POINTER(P)]),
     "zh_device_free": (C.c_int, [P, P]),
@@ -472,6 +480,42 @@ class DeviceContext:
         mv = memoryview(out)
         return [bytes(mv[o:o + n]) for o, n in rows]
 
+    def zstd_encode_batch_raw(self, sources, checksum=True, blocksize=0, stream=None, take=None):
+        """zh_zstd_encode_bound + zh_zstd_encode_batch over (device address, nbytes) pairs:
+        (the host buffer the frames arrived in, [(dst_off, cbytes)] per source).  `take(n)`: a
+        uint8 array of n bytes to receive them (default: a fresh one)."""
+        import numpy as np
+        n = len(sources)
+        arr = (A.zh_zstd_enc_frame * max(1, n))()
+        for i, (addr, nb) in enumerate(sources):
+            arr[i].src, arr[i].nbytes = addr, int(nb)
+        prm = A.zh_zstd_enc_params(1 if checksum else 0, int(blocksize))
+        bound = self.L.zh_zstd_encode_bound(arr, n, C.byref(prm))
+        if bound < 0:
+            raise ZhError(int(-bound), "zstd encode: checksum 0 or 1, blocksize >= 0, sizes >= 0")
+        out = (take or (lambda k: np.empty(k, np.uint8)))(max(1, bound))
+        err = C.create_string_buffer(1024)
+        check(self.L.zh_zstd_encode_batch(self.h, arr, n, C.byref(prm), P(out.ctypes.data),
+                                          bound, P(stream), err, 1024), err)
+        return out, [(int(arr[i].dst_off), int(arr[i].cbytes)) for i in range(n)]
+
+    def zstd_encode_batch(self, sources, checksum=True, blocksize=0, stream=None, take=None):
+        """The zstd frames of (device address, nbytes) sources as a list of bytes."""
+        out, rows = self.zstd_encode_batch_raw(sources, checksum, blocksize, stream, take)
+        mv = memoryview(out)
+        return [bytes(mv[o:o + n]) for o, n in rows]
+
+    def zstd_xxh64(self, sources):
+        """zh_debug_zstd_xxh64: XXH64 (seed 0) of (device address, nbytes) buffers by the hash
+        kernel of the zstd batch."""
+        n = len(sources)
+        arr = (A.zh_zstd_enc_frame * max(1, n))()
+        for i, (addr, nb) in enumerate(sources):
+            arr[i].src, arr[i].nbytes = addr, int(nb)
+        out = (U64 * max(1, n))()
+        check(self.L.zh_debug_zstd_xxh64(self.h, arr, n, out))
+        return [int(out[i]) for i in range(n)]
+
     def host_staging(self, nbytes):
         """zh_host_staging: the context's page-locked staging (valid until the next call)."""
         p = P()
@@ -625,6 +669,21 @@ def blosc_batch_plan(frames):
         check(int(-total), err)
     return int(total), [(arr[i].dst_off, arr[i].nbytes, arr[i].where)
                         for i in range(len(frames))]
+
+
+def zstd_compress(data, checksum=True, blocksize=0):
+    """zh_zstd_compress (no device): one zstd frame of `data`, its content cut into blocks of
+    `blocksize` bytes (0: the default) that are compressed on their own."""
+    L = lib()
+    data = bytes(data)
+    prm = A.zh_zstd_enc_params(1 if checksum else 0, int(blocksize))
+    n = SZ()
+    err = C.create_string_buffer(256)
+    check(L.zh_zstd_compress(data, len(data), C.byref(prm), None, 0, C.byref(n), err, 256), err)
+    out = (C.c_char * n.value)()
+    check(L.zh_zstd_compress(data, len(data), C.byref(prm), out, n.value, C.byref(n), err, 256),
+          err)
+    return bytes(out[:n.value])
 
 
 def blosc_compress(data, typesize, shuffle, blocksize=0):

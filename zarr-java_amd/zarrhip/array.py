@@ -11,8 +11,9 @@ chunk codec work done by the HIP path through the C-ABI (libzarrhip.so).
 Byte-to-byte compressors stay on the host (north star): their frames are decoded here and
 the raw chunk bytes are handed to the device — except blosc frames, which
 one batched call decodes on the device when blosc is the chain's only host stage
-(ZH_BLOSC_DEVICE, zh_blosc_decode_batch), and blosc LZ4 frames, which Array.write compresses on
-the device (ZH_BLOSC_ENCODE_DEVICE, zh_blosc_encode_batch).
+(ZH_BLOSC_DEVICE, zh_blosc_decode_batch), and blosc LZ4 and zstd frames, which Array.write
+compresses on the device (ZH_BLOSC_ENCODE_DEVICE, zh_blosc_encode_batch; ZH_ZSTD_ENCODE_DEVICE,
+zh_zstd_encode_batch).
 """
 import atexit
 import ctypes as C
@@ -26,7 +27,7 @@ import numpy as np
 
 from . import _abi as A
 from . import _lib
-from .codecs import BloscCodec, device_chain, host_bb_decode, host_bb_encode
+from .codecs import BloscCodec, ZstdCodec, device_chain, host_bb_decode, host_bb_encode
 from .errors import UnsupportedChainError, ZarrException, raise_for
 from .metadata import ZARR_JSON, ArrayMetadata
 
@@ -42,6 +43,9 @@ BLOSC_DEVICE_DEFAULT = "1"
 # It stays "1" whatever the write times say: the stored size is what the codec was asked for,
 # and both routes store the same bytes (DESIGN.md "Blosc frames encoded on the device").
 BLOSC_ENCODE_DEVICE_DEFAULT = "1"
+# ZH_ZSTD_ENCODE_DEVICE: the same for a zstd chain (zh_zstd_encode_batch), and "1" for the same
+# reason (DESIGN.md "Zstd frames encoded on the device").
+ZSTD_ENCODE_DEVICE_DEFAULT = "1"
 
 
 class _Deferred:
@@ -754,14 +758,15 @@ class Array:
             except _lib.ZhError as e:
                 raise_for(e)
             self.last_write_info = {"blosc_device_frames": 0, "blosc_host_frames": 0,
+                                    "zstd_device_frames": 0, "zstd_host_frames": 0,
                                     "raw_bytes": sum(sizes), "stored_bytes": sum(sizes)}
             return
         L = _lib.lib()
         cap = L.zh_array_encoded_bound(C.byref(self.zmeta))
         src = dev.malloc(max(1, data.nbytes))
         bufs = []
-        info = {"blosc_device_frames": 0, "blosc_host_frames": 0, "raw_bytes": 0,
-                "stored_bytes": 0}
+        info = {"blosc_device_frames": 0, "blosc_host_frames": 0, "zstd_device_frames": 0,
+                "zstd_host_frames": 0, "raw_bytes": 0, "stored_bytes": 0}
         try:
             dev.memcpy(src, data.ctypes.data, data.nbytes, 0)
             bufs = [dev.malloc(cap) for _ in coords]
@@ -769,8 +774,8 @@ class Array:
                 sizes = dev.array_write(self.zmeta, src, offset, shape, [(b, cap) for b in bufs])
             except _lib.ZhError as e:
                 raise_for(e)
-            stored = self._blosc_frames_device(dev, bufs, sizes, info) \
-                if self._blosc_encode_device() else {}
+            kind = self._encode_device()
+            stored = self._frames_device(dev, bufs, sizes, info, kind) if kind else {}
             for k, (c, b, sz) in enumerate(zip(coords, bufs, sizes)):
                 h = self._handle(c)
                 if sz == 0 and not keep_fill:
@@ -810,28 +815,48 @@ class Array:
             if info is not None:
                 info["blosc_host_frames"] += 1
             return bb[0].encode(enc, self.metadata.data_type.getByteCount())
+        if info is not None and self._zstd_chain():
+            info["zstd_host_frames"] += 1
         return host_bb_encode(bb, enc)
 
-    def _blosc_encode_device(self):
-        """Array.write makes the chain's blosc frames on the device (zh_blosc_encode_batch):
-        blosc is the only host byte-to-byte stage, its cname is lz4 / lz4hc (the one blosc
-        compressor written here; clevel is not honoured), one device is in use and
-        ZH_BLOSC_ENCODE_DEVICE is not "0"."""
-        if not self._blosc_chain() or len(devices()) != 1 or \
-                os.environ.get("ZH_BLOSC_ENCODE_DEVICE", BLOSC_ENCODE_DEVICE_DEFAULT) == "0":
-            return False
+    def _zstd_chain(self):
+        """The chain's host byte-to-byte stages are exactly one ZstdCodec."""
         bb = self.chain.inner_host_bb if self.chain.chain["sharded"] else self.chain.host_bb
-        return bb[0].lz4()
+        return len(bb) == 1 and isinstance(bb[0], ZstdCodec)
 
-    def _blosc_frames_device(self, dev, bufs, sizes, info):
-        """The stored objects of the chunks with sz > 0, their blosc frames compressed on the
-        device in one batch over the chunk buffers: {chunk number: bytes}.  Unsharded: the
-        chunk is one frame.  Sharded: only the stored index comes back as it is; every present
-        entry is one frame, and the shard is put together as _wrap_inner does."""
+    def _encode_device(self):
+        """"blosc" / "zstd" when Array.write makes the chain's frames on the device
+        (zh_blosc_encode_batch / zh_zstd_encode_batch), else None: the codec is the only host
+        byte-to-byte stage, one device is in use and the codec's switch (ZH_BLOSC_ENCODE_DEVICE /
+        ZH_ZSTD_ENCODE_DEVICE) is not "0".  Blosc: its cname is lz4 / lz4hc (the one blosc
+        compressor written here; clevel is not honoured, as zstd's level is not)."""
+        if len(devices()) != 1:
+            return None
+        bb = self.chain.inner_host_bb if self.chain.chain["sharded"] else self.chain.host_bb
+        if self._blosc_chain():
+            on = os.environ.get("ZH_BLOSC_ENCODE_DEVICE", BLOSC_ENCODE_DEVICE_DEFAULT) != "0"
+            return "blosc" if on and bb[0].lz4() else None
+        if self._zstd_chain():
+            on = os.environ.get("ZH_ZSTD_ENCODE_DEVICE", ZSTD_ENCODE_DEVICE_DEFAULT) != "0"
+            return "zstd" if on else None
+        return None
+
+    def _frames_device(self, dev, bufs, sizes, info, kind):
+        """The stored objects of the chunks with sz > 0, their blosc or zstd frames (`kind`)
+        compressed on the device in one batch over the chunk buffers: {chunk number: bytes}.
+        Unsharded: the chunk is one frame.  Sharded: only the stored index comes back as it is;
+        every present entry is one frame, and the shard is put together as _wrap_inner does."""
         ch = self.chain.chain
         sharded = ch["sharded"]
         codec = (self.chain.inner_host_bb if sharded else self.chain.host_bb)[0]
-        ts, shuffle, blocksize = codec.enc_params(self.metadata.data_type.getByteCount())
+        if kind == "blosc":
+            ts, shuffle, blocksize = codec.enc_params(self.metadata.data_type.getByteCount())
+
+            def batch(sources, take):
+                return dev.blosc_encode_batch(sources, ts, shuffle, blocksize, take=take)
+        else:
+            def batch(sources, take):
+                return dev.zstd_encode_batch(sources, bool(codec.checksum), take=take)
         sources, shards = [], {}
         if sharded:
             n_in = self._n_inner()
@@ -850,15 +875,14 @@ class Array:
             sources.extend((b + off, nb) for off, nb in ents if off != 2 ** 64 - 1)
         lease = []  # the frames land in a pooled buffer: no fresh pages per write
         try:
-            frames = dev.blosc_encode_batch(sources, ts, shuffle, blocksize,
-                                            take=lambda n: staging_pool.take(n, lease))
+            frames = batch(sources, lambda n: staging_pool.take(n, lease))
         except _lib.ZhError as e:
             if e.status == A.ZH_EINVAL:
-                raise ZarrException(f"Error in encoding blosc: {e}") from None
+                raise ZarrException(f"Error in encoding {kind}: {e}") from None
             raise_for(e)
         finally:
             staging_pool.give(lease)
-        info["blosc_device_frames"] += len(frames)
+        info[kind + "_device_frames"] += len(frames)
         info["raw_bytes"] += sum(nb for _, nb in sources)
         if not sharded:
             return dict(zip([k for k, sz in enumerate(sizes) if sz > 0], frames))

@@ -323,8 +323,9 @@ class ZstdCodec(Codec):
     """ZstdCodec (M/core/codec/core/ZstdCodec.java:14-22, M/v3/codec/core/ZstdCodec.java) —
     host only.  Decode: zh_zstd_decompress, a from-scratch RFC 8878 frame decoder in the
     library (zstd-jni / libzstd in the reference); the content checksum is verified when a
-    frame carries one.  Encode writes frames of raw (stored) blocks with the content size and,
-    per `checksum`, the XXH64 checksum — valid zstd for every reader (no compressor here)."""
+    frame carries one.  Encode: zh_zstd_compress, the host form of the block writer Array.write
+    runs on the device (greedy LZ, raw literals, predefined FSE tables; blocks that do not
+    shrink are raw blocks); `level` is not honoured, the metadata keeps it."""
     name, kind = "zstd", "bb"
 
     def __init__(self, level=5, checksum=True):
@@ -354,16 +355,8 @@ class ZstdCodec(Codec):
         return bytes(out)[:n.value]
 
     def encode(self, b):
-        import ctypes as C
-        from ._lib import check, lib
-        b = bytes(b)
-        L = lib()
-        n = C.c_size_t()
-        check(L.zh_zstd_compress_raw(b, len(b), 1 if self.checksum else 0, None, 0, C.byref(n)))
-        out = (C.c_char * n.value)()
-        check(L.zh_zstd_compress_raw(b, len(b), 1 if self.checksum else 0, out, n.value,
-                                     C.byref(n)))
-        return bytes(out)
+        from ._lib import zstd_compress
+        return zstd_compress(b, bool(self.checksum))
 
     def to_json(self):
         return {"name": "zstd", "configuration": {"level": self.level, "checksum": self.checksum}}
