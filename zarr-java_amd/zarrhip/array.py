@@ -775,6 +775,15 @@ class Array:
             except _lib.ZhError as e:
                 raise_for(e)
             kind = self._encode_device()
+            if kind and keep_fill:
+                # no fill value: an all-zero chunk is stored, never deleted — its frame is made
+                # in the same batch as the others, not on the host
+                nb = int(np.prod(cs)) * self.metadata.data_type.getByteCount()
+                for k, sz in enumerate(sizes):
+                    if sz == 0:
+                        dev.memset(bufs[k], 0, nb)
+                        sizes[k] = nb
+                dev.sync()
             stored = self._frames_device(dev, bufs, sizes, info, kind) if kind else {}
             for k, (c, b, sz) in enumerate(zip(coords, bufs, sizes)):
                 h = self._handle(c)
