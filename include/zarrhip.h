@@ -738,6 +738,58 @@ int zh_zstd_encode_batch(zh_ctx* ctx, zh_zstd_enc_frame* frames, int64_t n,
 double zh_debug_zstd_encode_kernel_ms(void);
 int zh_debug_zstd_xxh64(zh_ctx* ctx, const zh_zstd_enc_frame* frames, int64_t n, uint64_t* out);
 
+/* ---- zstd frames decoded on the device, a batch at a time -----------------------------
+ * The read side of the batch above, in the shape of zh_blosc_decode_batch.  A stored chunk that
+ * is exactly one zstd frame with a Frame_Content_Size, no dictionary and a block chain that ends
+ * at its last byte (its checksum included) is decoded on the device: one wavefront per frame
+ * runs the block decoder (raw / RLE / compressed blocks; raw, RLE, Huffman and treeless
+ * literals; predefined, RLE, FSE and repeat sequence tables) with its tables in LDS, and the
+ * content checksum is verified by the hash kernel of zh_zstd_encode_batch.  Everything else
+ * (concatenated or skippable frames, no content size, a content size the block headers cannot
+ * produce, a header walk that fails) is decoded by zh_zstd_decompress on the host inside the
+ * call and copied up.  The decoded frames lie in one device buffer at dst_off. */
+typedef struct zh_zstd_frame {
+  const void* src;   /* the stored frame, host memory                               */
+  int64_t srclen;
+  int64_t dst_off;   /* out (plan): offset in the batch destination, 256-B aligned  */
+  int64_t nbytes;    /* out (plan): decoded size                                    */
+  int32_t where;     /* out (plan): 0 device, 1 host fallback (zh_zstd_decompress into
+                        pinned staging, then H2D).  zh_zstd_decode_batch also sets 1 on a
+                        frame its kernel refused and the host decoder then accepted    */
+  int32_t status;    /* out: ZH_OK or this frame's error                            */
+} zh_zstd_frame;
+
+/* No device needed: runs zh_zstd_decompress's size query on every frame (its status and text
+ * for the first bad frame in batch order; that frame's status field is set), walks the frame
+ * and block headers (no entropy decoding), fills dst_off / nbytes / where, and returns the
+ * destination bytes or -zh_status. */
+int64_t zh_zstd_batch_plan(zh_zstd_frame* frames, int64_t n, char* err, size_t errlen);
+
+/* Plans as above, stages the compressed bytes H2D through the context's pinned ring, decodes on
+ * `stream` (NULL: the context's) in slabs of at most 128 MiB of decoded bytes (a larger frame is
+ * its own slab), waits, and reports the first failing frame in batch order with
+ * zh_zstd_decompress's status and text: a frame the kernel flags (not-ok, or a checksum
+ * mismatch) is decoded again by the host decoder, which names the error or, if it accepts the
+ * frame, supplies the bytes.  dst is device memory of dstcap >= the plan's bytes.  After a
+ * failed call dst is undefined; the context stays usable. */
+int zh_zstd_decode_batch(zh_ctx* ctx, zh_zstd_frame* frames, int64_t n, void* dst,
+                         int64_t dstcap, void* stream, char* err, size_t errlen);
+
+/* Diagnostic: milliseconds the decode and checksum kernels of the last successful
+ * zh_zstd_decode_batch in this process took, by device events, summed over its slabs (-1: none
+ * yet). */
+double zh_debug_zstd_decode_kernel_ms(void);
+
+/* Diagnostic, no device: the blocks of one device-decoded frame as rows of 10 int64: block
+ * type (0 raw, 1 RLE, 2 compressed), stored size, decoded size (-1: a compressed block does not
+ * say), and for a compressed block the literals type (0 raw, 1 RLE, 2 Huffman, 3 treeless), the
+ * number of Huffman streams (0, 1 or 4), the regenerated literals size, the sequence count and
+ * the LL / OF / ML table modes (0 predefined, 1 RLE, 2 FSE, 3 repeat); -1 where a field does not
+ * apply.  Writes up to `cap` rows to `rows` (may be NULL) and returns their number, or
+ * -ZH_EUNSUPPORTED for a frame the plan sends to the host. */
+int64_t zh_debug_zstd_blocks(const void* src, size_t srclen, int64_t* rows, int64_t cap,
+                             char* err, size_t errlen);
+
 /* dst block b ← src block src_block[b] (device buffers, blocks of block_bytes, a multiple of
  * 16; 16-byte aligned; src_block on the host), synchronous: re-lays out encoded shards, e.g.
  * the bench's shuffled inner-chunk order. */

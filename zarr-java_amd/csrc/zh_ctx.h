@@ -269,6 +269,9 @@ void pipeline_release(zh_ctx* ctx);  // zh_ctx_destroy: streams and rings
 // The pipelined read's copy lanes (ZH_PIPE_THREADS) and ring window (ZH_PIPE_CHUNK_KB), with
 // both rings holding two slots per lane and the copy streams created (caller holds ctx->mu).
 int pipe_out_ring(zh_ctx* ctx, int* lanes, int64_t* window);
+// zh_zstd_enc_kernels.hip: XXH64 (seed 0) of n device buffers, one wave each, on stream s;
+// d_jobs: n x {uint64 address, uint64 nbytes} and d_hashes[n], both in device memory.
+int zstd_hash_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint64_t* d_hashes);
 // One region over several contexts (zh_array_read_multi_routed / zh_array_read_pieces_multi).
 int read_multi_impl(zh_ctx* const* ctxs, int ndev, int root, const zh_array_meta* meta,
                     const SrcDesc* chunks, int64_t nchunks, const int64_t* offset,

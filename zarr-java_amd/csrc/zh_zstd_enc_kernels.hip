@@ -435,6 +435,15 @@ int64_t bound_of(const zh_zstd_enc_frame* frames, int64_t n, const zh_zstd_enc_p
 
 }  // namespace
 
+// The hash kernel for the decode batch (zh_zstd_dec_kernels.hip), which verifies checksums.
+int zh::zstd_hash_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint64_t* d_hashes) {
+  static_assert(sizeof(HashJob) == 16, "the decode batch builds these rows");
+  if (n == 0) return ZH_OK;
+  hipLaunchKernelGGL(zstd_xxh64_kernel, dim3((n + kWaves - 1) / kWaves), dim3(kThreads), 0, s,
+                     (const HashJob*)d_jobs, n, d_hashes);
+  return hipGetLastError() == hipSuccess ? ZH_OK : ZH_EHIP;
+}
+
 extern "C" {
 
 int64_t zh_zstd_encode_bound(const zh_zstd_enc_frame* frames, int64_t n,

@@ -92,6 +92,12 @@ class zh_blosc_frame(C.Structure):
                 ("nbytes", C.c_int64), ("where", C.c_int32), ("status", C.c_int32)]
 
 
+class zh_zstd_frame(C.Structure):
+    """One zstd frame of a batched device decode (zarrhip.h zh_zstd_frame)."""
+    _fields_ = [("src", C.c_void_p), ("srclen", C.c_int64), ("dst_off", C.c_int64),
+                ("nbytes", C.c_int64), ("where", C.c_int32), ("status", C.c_int32)]
+
+
 class zh_blosc_enc_params(C.Structure):
     """How blosc1 LZ4 frames are written (zarrhip.h zh_blosc_enc_params)."""
     _fields_ = [("typesize", C.c_int32), ("shuffle", C.c_int32), ("blocksize", C.c_int32)]

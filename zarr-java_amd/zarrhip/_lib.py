@@ -115,6 +115,10 @@ _SIGS = {
                                        C.POINTER(A.zh_zstd_enc_params), P, I64, P, CH, SZ]),
     "zh_debug_zstd_encode_kernel_ms": (C.c_double, []),
     "zh_debug_zstd_xxh64": (C.c_int, [P, C.POINTER(A.zh_zstd_enc_frame), I64, C.POINTER(U64)]),
+    "zh_zstd_batch_plan": (I64, [C.POINTER(A.zh_zstd_frame), I64, CH, SZ]),
+    "zh_zstd_decode_batch": (C.c_int, [P, C.POINTER(A.zh_zstd_frame), I64, P, I64, P, CH, SZ]),
+    "zh_debug_zstd_decode_kernel_ms": (C.c_double, []),
+    "zh_debug_zstd_blocks": (I64, [P, SZ, PI64, I64, CH, SZ]),
     "zh_device_malloc": (C.c_int, [P, SZ, C.POINTER(P)]),
     "zh_device_malloc_ex": (C.c_int, [P, SZ, C.c_uint, C.POINTER(P)]),
     "zh_device_free": (C.c_int, [P, P]),
@@ -451,6 +455,40 @@ class DeviceContext:
         del keep
         return ptr, [(arr[i].dst_off, arr[i].nbytes, arr[i].where) for i in range(len(frames))]
 
+    def zstd_decode_batch(self, frames, stream=None):
+        """zh_zstd_batch_plan + zh_zstd_decode_batch over zstd frames (bytes-like, or (address,
+        nbytes) pairs of host memory the caller keeps alive): returns the device buffer holding
+        every decoded frame and, per frame, (dst_off, nbytes, where).  The caller frees the
+        buffer (self.free)."""
+        arr, keep = frame_array(frames, A.zh_zstd_frame)
+        err = C.create_string_buffer(1024)
+        n = len(frames)
+        total = self.L.zh_zstd_batch_plan(arr, n, err, 1024)
+        # the first frame in batch order that the plan refuses, or whose content size no frame
+        # of its length can hold (ZstdCodec.decode's bound: never size an allocation by it)
+        bad = None
+        if total < 0:
+            k = next(i for i in range(n) if arr[i].status != A.ZH_OK)
+            bad = (k, ZhError(int(-total), err.value.decode()))
+        for i in range(bad[0] if bad else n):
+            if arr[i].nbytes > arr[i].srclen * 32768 + (64 << 10):
+                bad = (i, ZhError(A.ZH_EDATA, f"frame content size {arr[i].nbytes} exceeds what "
+                                              f"{arr[i].srclen} bytes of frame can hold"))
+                break
+        if bad is not None:  # after the errors of the frames before it
+            if bad[0] > 0:
+                self.free(self.zstd_decode_batch(frames[:bad[0]], stream)[0])
+            raise bad[1]
+        ptr = self.malloc(max(256, total), A.ZH_MALLOC_PLAIN)
+        try:
+            check(self.L.zh_zstd_decode_batch(self.h, arr, len(frames), P(ptr), max(256, total),
+                                              P(stream), err, 1024), err)
+        except BaseException:
+            self.free(ptr)
+            raise
+        del keep
+        return ptr, [(arr[i].dst_off, arr[i].nbytes, arr[i].where) for i in range(len(frames))]
+
     def blosc_encode_batch_raw(self, sources, typesize, shuffle, blocksize=0, stream=None,
                                take=None):
         """zh_blosc_encode_bound + zh_blosc_encode_batch over (device address, nbytes) pairs:
@@ -645,10 +683,10 @@ def array_read_pieces_multi(ctxs, meta, shards, offset, shape, out, flags, root=
     return list(routes)
 
 
-def blosc_frame_array(frames):
-    """ctypes zh_blosc_frame[] for bytes-like frames or (address, nbytes) pairs; returns
-    (array, keepalive)."""
-    arr = (A.zh_blosc_frame * max(1, len(frames)))()
+def frame_array(frames, struct):
+    """ctypes struct[] (zh_blosc_frame or zh_zstd_frame) for bytes-like frames or (address,
+    nbytes) pairs; returns (array, keepalive)."""
+    arr = (struct * max(1, len(frames)))()
     keep = []
     for i, f in enumerate(frames):
         if isinstance(f, tuple):
@@ -658,6 +696,34 @@ def blosc_frame_array(frames):
         keep.append(b)
         arr[i].src, arr[i].srclen = C.addressof(b), len(f)
     return arr, keep
+
+
+def blosc_frame_array(frames):
+    return frame_array(frames, A.zh_blosc_frame)
+
+
+def zstd_batch_plan(frames):
+    """zh_zstd_batch_plan (no device): (destination bytes, [(dst_off, nbytes, where)])."""
+    arr, keep = frame_array(frames, A.zh_zstd_frame)
+    err = C.create_string_buffer(1024)
+    total = lib().zh_zstd_batch_plan(arr, len(frames), err, 1024)
+    if total < 0:
+        check(int(-total), err)
+    return int(total), [(arr[i].dst_off, arr[i].nbytes, arr[i].where)
+                        for i in range(len(frames))]
+
+
+def zstd_blocks(frame):
+    """zh_debug_zstd_blocks (no device): the block rows of one frame, 10 ints each."""
+    L = lib()
+    b = (C.c_char * max(1, len(frame))).from_buffer_copy(bytes(frame) or b"\0")
+    err = C.create_string_buffer(1024)
+    n = L.zh_debug_zstd_blocks(b, len(frame), None, 0, err, 1024)
+    if n < 0:
+        check(int(-n), err)
+    rows = (C.c_int64 * max(1, 10 * n))()
+    L.zh_debug_zstd_blocks(b, len(frame), rows, n, err, 1024)
+    return [tuple(rows[10 * k:10 * k + 10]) for k in range(n)]
 
 
 def blosc_batch_plan(frames):

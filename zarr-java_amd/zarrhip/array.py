@@ -9,9 +9,10 @@ chunk codec work done by the HIP path through the C-ABI (libzarrhip.so).
   access()                   M/core/Array.java:483-536   (ArrayAccessor)
 
 Byte-to-byte compressors stay on the host (north star): their frames are decoded here and
-the raw chunk bytes are handed to the device — except blosc frames, which
-one batched call decodes on the device when blosc is the chain's only host stage
-(ZH_BLOSC_DEVICE, zh_blosc_decode_batch), and blosc LZ4 and zstd frames, which Array.write
+the raw chunk bytes are handed to the device — except blosc and zstd frames,
+which one batched call decodes on the device when the codec is the chain's only host stage
+(ZH_BLOSC_DEVICE, zh_blosc_decode_batch; ZH_ZSTD_DEVICE, zh_zstd_decode_batch), and blosc LZ4 and
+zstd frames, which Array.write
 compresses on the device (ZH_BLOSC_ENCODE_DEVICE, zh_blosc_encode_batch; ZH_ZSTD_ENCODE_DEVICE,
 zh_zstd_encode_batch).
 """
@@ -38,6 +39,15 @@ _ctx_lock = threading.Lock()
 # device in one batch (zh_blosc_decode_batch) instead of decoding them here one at a time.
 # The default follows the measurement in DESIGN.md ("Blosc frames on the device").
 BLOSC_DEVICE_DEFAULT = "1"
+# ZH_ZSTD_DEVICE: the same for chains whose only host byte-to-byte stage is zstd
+# (zh_zstd_decode_batch).  "0": the host route; "2": every eligible read goes to the device;
+# "1" (the default): the rule of DESIGN.md ("Zstd frames on the device"), a read goes to the
+# device when it holds at least ZSTD_DEVICE_MIN_FRAMES frames.  In the record
+# (profiles/zstd_decode/lab.json) few large frames lose outright and many small frames do not
+# clear the rule's margin on every array, so the default sends nothing to the device:
+# ZSTD_DEVICE_MIN_FRAMES is None, and the device route is behind ZH_ZSTD_DEVICE=2.
+ZSTD_DEVICE_DEFAULT = "1"
+ZSTD_DEVICE_MIN_FRAMES = None
 # ZH_BLOSC_ENCODE_DEVICE: Array.write compresses a blosc LZ4 chain's frames on the device in one
 # batch (zh_blosc_encode_batch) instead of copying every raw chunk back and compressing it here.
 # It stays "1" whatever the write times say: the stored size is what the codec was asked for,
@@ -62,6 +72,15 @@ def _raise_blosc(err):
         raise UnsupportedChainError(str(err)) from None
     if err.status in (A.ZH_EDATA, A.ZH_EINVAL):
         raise ZarrException(f"Error in decoding blosc: {err}") from None
+    raise_for(err)
+
+
+def _raise_zstd(err):
+    """A _lib.ZhError of the batched zstd decode as ZstdCodec.decode raises it."""
+    if err.status == A.ZH_EUNSUPPORTED:
+        raise UnsupportedChainError(str(err)) from None
+    if err.status in (A.ZH_EDATA, A.ZH_EINVAL):
+        raise ZarrException(f"Error in decoding zstd: {err}") from None
     raise_for(err)
 
 
@@ -330,7 +349,7 @@ class Array:
         reference's "Could not load byte data for chunk").  `full`: the part is the whole shard
         (decodePartial → chunkHandle.read() → ByteBufferDataProvider, :246-251, 301-331), so
         the shard is the file as it is — an entry beyond its bytes is an error (Q14), not a
-        zero-padded range.  `collect` (the device blosc route): the inner chunks' frames are
+        zero-padded range.  `collect` (the device blosc / zstd route): the inner chunks' frames are
         kept as read, as pieces (offset, stored bytes, frame, None), for one batched decode of
         the whole read.  Returns a ShardSource plus the buffers it points into, or None for
         a missing shard."""
@@ -513,8 +532,12 @@ class Array:
                                      "device_s": time.perf_counter() - t1, "files": True}
             return
         if self._blosc_device(devs):
-            self._read_blosc_device(coords, offset, shape, out_addr, flags, devs[0], parallel,
-                                    t_enter, t0)
+            self._read_frames_device(coords, offset, shape, out_addr, flags, devs[0], parallel,
+                                     t_enter, t0, devs[0].blosc_decode_batch, _raise_blosc, "blosc")
+            return
+        if self._zstd_device(devs, coords):
+            self._read_frames_device(coords, offset, shape, out_addr, flags, devs[0], parallel,
+                                     t_enter, t0, devs[0].zstd_decode_batch, _raise_zstd, "zstd")
             return
         lease = []  # staging buffers of this read, back to the pool after the device read
         sharded = self.chain.chain["sharded"]
@@ -533,8 +556,10 @@ class Array:
             else:
                 sources = [load(c) for c in coords]
             t1 = time.perf_counter()
-            n_blosc = 0 if not self._blosc_chain() else sum(
+            n_frames = sum(
                 0 if s is None else len(s[1].pieces) if s[0] == "pieces" else 1 for s in sources)
+            n_blosc = n_frames if self._blosc_chain() else 0
+            n_zstd = n_frames if self._zstd_chain() else 0
             keep = []
             try:
                 if sharded:  # index + pieces (or whole objects as one piece at 0)
@@ -580,7 +605,8 @@ class Array:
             staging_pool.give(lease)
         self.last_read_timing = {"prep_s": t0 - t_enter, "stage_s": t1 - t0,
                                  "device_s": time.perf_counter() - t1,
-                                 "blosc_device_frames": 0, "blosc_host_frames": n_blosc}
+                                 "blosc_device_frames": 0, "blosc_host_frames": n_blosc,
+                                 "zstd_device_frames": 0, "zstd_host_frames": n_zstd}
 
     def _blosc_chain(self):
         """The chain's host byte-to-byte stages are exactly one BloscCodec (v3 or v2)."""
@@ -591,11 +617,34 @@ class Array:
         return (len(devs) == 1 and self._blosc_chain() and
                 os.environ.get("ZH_BLOSC_DEVICE", BLOSC_DEVICE_DEFAULT) != "0")
 
-    def _read_blosc_device(self, coords, offset, shape, out_addr, flags, dev, parallel, t_enter,
-                           t0):
-        """_read_into for a blosc chain on one device: the store reads of every chunk (a
-        shard: its index check and per-entry range reads), one zh_blosc_decode_batch over all
-        frames of the read, then the device read over sources in the batch buffer."""
+    def _zstd_chain(self):
+        """The chain's host byte-to-byte stages are exactly one ZstdCodec."""
+        bb = self.chain.inner_host_bb if self.chain.chain["sharded"] else self.chain.host_bb
+        return len(bb) == 1 and isinstance(bb[0], ZstdCodec)
+
+    def _zstd_device(self, devs, coords=()):
+        """One device, a zstd chain and ZH_ZSTD_DEVICE: "0" never, "2" always, "1" when the read
+        has at least ZSTD_DEVICE_MIN_FRAMES frames (a shard counts its inner chunks)."""
+        if len(devs) != 1 or not self._zstd_chain():
+            return False
+        mode = os.environ.get("ZH_ZSTD_DEVICE", ZSTD_DEVICE_DEFAULT)
+        if mode == "0":
+            return False
+        if mode == "2":
+            return True
+        if ZSTD_DEVICE_MIN_FRAMES is None:
+            return False
+        per = self._n_inner() if self.chain.chain["sharded"] else 1
+        return len(coords) * per >= ZSTD_DEVICE_MIN_FRAMES
+
+    def _read_frames_device(self, coords, offset, shape, out_addr, flags, dev, parallel, t_enter,
+                            t0, decode_batch, raise_frame, codec):
+        """_read_into for a chain whose only host stage is blosc or zstd, on one device: the
+        store reads of every chunk (a shard: its index check and per-entry range reads), one
+        batched decode (`decode_batch`: DeviceContext.blosc_decode_batch / zstd_decode_batch) over
+        all frames of the read, then the device read over sources in the batch buffer.
+        `raise_frame` raises a frame's _lib.ZhError as the codec's host decode does; `codec`
+        names the counters of last_read_timing."""
         sharded = self.chain.chain["sharded"]
         cs = self.metadata.chunk_shape
 
@@ -631,10 +680,10 @@ class Array:
         ptr = iptr = None
         try:
             try:
-                ptr, rows = dev.blosc_decode_batch(
+                ptr, rows = decode_batch(
                     [(int(v.ctypes.data), len(f)) for v, f in zip(views, frames)])
             except _lib.ZhError as e:
-                _raise_blosc(e)
+                raise_frame(e)
             if bad is not None:
                 raise sources[bad].exc
             it = iter(rows)
@@ -683,8 +732,10 @@ class Array:
             del views, sources
         self.last_read_timing = {
             "prep_s": t0 - t_enter, "stage_s": t1 - t0, "device_s": time.perf_counter() - t1,
-            "blosc_device_frames": sum(1 for r in rows if r[2] != 1),
-            "blosc_host_frames": sum(1 for r in rows if r[2] == 1)}
+            "blosc_device_frames": 0, "blosc_host_frames": 0,
+            "zstd_device_frames": 0, "zstd_host_frames": 0,
+            codec + "_device_frames": sum(1 for r in rows if r[2] != 1),
+            codec + "_host_frames": sum(1 for r in rows if r[2] == 1)}
 
     def readChunk(self, coords):
         """core.Array.readChunk (M/core/Array.java:167-182)."""
