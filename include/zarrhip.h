@@ -681,7 +681,11 @@ double zh_debug_blosc_encode_kernel_ms(void);
  * zstd compressor of blosc frames (BloscCodec.java; CodecBuilder.withBlosc() defaults to
  * cname "zstd", M/v3/codec/CodecBuilder.java:58-60).  One or more frames (skippable frames
  * skipped); the XXH64 content checksum is verified when a frame carries one; frames that need
- * a dictionary → ZH_EUNSUPPORTED.  dst == NULL: *dstlen = the decoded size.
+ * a dictionary → ZH_EUNSUPPORTED.  dst == NULL: *dstlen = the decoded size (the declared content
+ * sizes, or a pass that stores nothing for a frame that declares none).  A frame is decoded by
+ * the decoder the device batch below runs (csrc/zh_zstd_dec.h), here on one lane; this call adds
+ * the loop over frames, the checksum comparison and the status and text of each reason.  After
+ * a failure *dstlen says nothing.
  * zh_zstd_compress_raw writes a valid frame of raw (stored) blocks with the content size and,
  * if asked, the checksum (the write path's encoder; no compression); dst == NULL: the size.
  * zh_xxh64: XXH64 of a buffer (the checksum's hash). */
@@ -755,7 +759,7 @@ typedef struct zh_zstd_frame {
   int64_t nbytes;    /* out (plan): decoded size                                    */
   int32_t where;     /* out (plan): 0 device, 1 host fallback (zh_zstd_decompress into
                         pinned staging, then H2D).  zh_zstd_decode_batch also sets 1 on a
-                        frame its kernel refused and the host decoder then accepted    */
+                        frame its kernel refused and zh_zstd_decompress then accepted  */
   int32_t status;    /* out: ZH_OK or this frame's error                            */
 } zh_zstd_frame;
 
@@ -768,9 +772,10 @@ int64_t zh_zstd_batch_plan(zh_zstd_frame* frames, int64_t n, char* err, size_t e
 /* Plans as above, stages the compressed bytes H2D through the context's pinned ring, decodes on
  * `stream` (NULL: the context's) in slabs of at most 128 MiB of decoded bytes (a larger frame is
  * its own slab), waits, and reports the first failing frame in batch order with
- * zh_zstd_decompress's status and text: a frame the kernel flags (not-ok, or a checksum
- * mismatch) is decoded again by the host decoder, which names the error or, if it accepts the
- * frame, supplies the bytes.  dst is device memory of dstcap >= the plan's bytes.  After a
+ * zh_zstd_decompress's status and text: the kernel runs the decoder zh_zstd_decompress runs and
+ * leaves its reason in the frame's flag; a flagged frame (or a checksum mismatch) goes through
+ * zh_zstd_decompress once more, which names the error or, if it accepts the frame, supplies the
+ * bytes. dst is device memory of dstcap >= the plan's bytes.  After a
  * failed call dst is undefined; the context stays usable. */
 int zh_zstd_decode_batch(zh_ctx* ctx, zh_zstd_frame* frames, int64_t n, void* dst,
                          int64_t dstcap, void* stream, char* err, size_t errlen);

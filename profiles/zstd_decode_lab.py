@@ -20,6 +20,9 @@ Timed, in one process, alternating, after one warm-up of each route, `--repeats`
     python profiles/zstd_decode_lab.py --host-only --tree <checkout> --out <json>
         the host route alone with another checkout's package (the parent commit:
         profiles/zstd_decode/parent_host.json)
+    python profiles/zstd_decode_lab.py --layouts sharded --gib 0.25 --tree <checkout> --out <json>
+        one layout at a size that runs in seconds, with this or another checkout's package, for
+        comparing two commits' kernels (profiles/zstd_decode/unify_lab.json)
 
 The default rule ("Zstd frames on the device"): a layout goes to the device by default
 only if the device route's median beats the host route's by more than the larger min-max spread of
@@ -54,6 +57,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "zstd_decode", "lab.json"))
     ap.add_argument("--tree", default=ROOT, help="the checkout whose package is timed")
     ap.add_argument("--host-only", action="store_true")
+    ap.add_argument("--layouts", default="sharded,chunked")
     ap.add_argument("--tmp", default="/dev/shm" if os.path.isdir("/dev/shm") else None)
     a = ap.parse_args()
     sys.path.insert(0, os.path.join(os.path.abspath(a.tree), "zarr-java_amd"))
@@ -111,6 +115,8 @@ def main():
         data3 = data2.reshape(-1)[:nshards * SHARD ** 3].reshape(nshards * SHARD, SHARD, SHARD)
         for layout, data, meta in (("sharded", data3, sharded_meta()),
                                    ("chunked", data2, chunked_meta())):
+            if layout not in a.layouts.split(","):
+                continue
             for writer in ("libzstd", "own"):
                 key = f"{name}-{layout}-{writer}"
                 root = tempfile.mkdtemp(prefix="zh_zstd_dec_lab_", dir=a.tmp)

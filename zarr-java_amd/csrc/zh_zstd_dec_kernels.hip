@@ -1,6 +1,6 @@
 // zh_zstd_dec_kernels.hip — batched device decode of zstd frames (zh_zstd_batch_plan /
-// zh_zstd_decode_batch / zh_debug_zstd_blocks); the decoder is zh_zstd_dec.h, the host decoder
-// zh_zstd_decompress (zh_zstd.cpp) names every status and text.
+// zh_zstd_decode_batch / zh_debug_zstd_blocks).  The decoder is zh_zstd_dec.h, the same templates
+// zh_zstd_decompress (zh_zstd.cpp) runs on one lane; that call has the status and text of a reason.
 //
 // The host walks every frame's headers once (zh_zd::walk_frame: no entropy decoding).  A single
 // frame with a content size, no dictionary and a block chain that ends exactly at its last byte
@@ -27,16 +27,17 @@
 //              the wave's own stores have reached the CU's L1 / L2 when vmcnt returns to 0, LDS
 //              operations of a wave complete in order).  It stands before every match copy and
 //              after every serial or parallel table / literal step.
-//     failure  not-ok stores 1 to the frame's flag (plain vector store).
+//     failure  the decoder's reason (zh_zd::Verdict, non-zero) goes to the frame's flag (plain
+//              vector store).
 //   zstd_xxh64_kernel (zh_zstd_enc_kernels.hip)  over the decoded frames that carry a checksum;
 //           the host compares the low 32 bits with the stored field.
-//   host    flagged or mismatching frames are decoded by zh_zstd_decompress in batch order: a
-//           failure is the call's status and text; a success is copied up and the frame's
-//           `where` becomes 1.
+//   host    flagged or mismatching frames go through zh_zstd_decompress in batch order (the flag's
+//           reason is not used yet): a failure is the call's status and text; a success is copied
+//           up and the frame's `where` becomes 1.
 // Slabs of at most kSlabBytes of decoded bytes bound the device memory (compressed bytes, literal
 // scratch <= the decoded bytes, small tables); a larger frame is its own slab.
 // Every DevFrame row is built on the host from checked sizes; the decoder checks every read
-// against the frame and every write against the frame's content size and its literal scratch.
+// against the frame and every write against the room the plan gave it and its literal scratch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -104,10 +105,16 @@ __global__ __launch_bounds__(kThreads) void zstd_decode_kernel(
   const DevFrame r = frames[f];
   ZdLanes p;
   p.l = threadIdx.x & 63;
-  const bool ok = zh_zd::decode_frame(src + r.src_off, (size_t)r.srclen, dst + r.dst_off,
-                                      (uint64_t)r.nbytes, lit + r.lit_off, (uint64_t)r.litcap,
-                                      work[wave], p);
-  if (p.l == 0) flags[f] = ok ? 0u : 1u;
+  zh_zd::Header h;
+  uint64_t made = 0;
+  size_t used = 0;
+  zh_zd::Verdict v = zh_zd::decode_frame(src + r.src_off, (size_t)r.srclen, dst + r.dst_off,
+                                         (uint64_t)r.nbytes, lit + r.lit_off, (uint64_t)r.litcap,
+                                         work[wave], p, &made, &used, &h);
+  // the plan's frame: exactly nbytes of content, and nothing after it
+  if (!v && made != (uint64_t)r.nbytes) v = zh_zd::kSizeMismatch;
+  if (!v && used != (size_t)r.srclen) v = zh_zd::kTrailingBytes;
+  if (p.l == 0) flags[f] = (uint32_t)v;
 }
 
 void put_err(char* err, size_t errlen, const char* msg) {
@@ -161,7 +168,7 @@ int plan_frames(zh_zstd_frame* frames, int64_t n, std::vector<zh_zd::Walk>* walk
 }
 
 // The device frames [f0, f1) of one slab: upload, decode, hash; flags[i] != 0 afterwards for a
-// frame the host decoder has to judge.
+// frame zh_zstd_decompress has to judge.
 int decode_slab(zh_ctx* ctx, hipStream_t s, Stager& sg, const zh_zstd_frame* frames,
                 const std::vector<zh_zd::Walk>& walks, const std::vector<int64_t>& ids,
                 uint8_t* dst, std::vector<uint32_t>& flags, double* ms) {
@@ -236,7 +243,8 @@ int decode_slab(zh_ctx* ctx, hipStream_t s, Stager& sg, const zh_zstd_frame* fra
   zh::ctx_release(ctx, dmem, got);
   if (rc != ZH_OK) return rc;
   for (size_t j = 0; j < jobs.size(); j++)
-    if ((uint32_t)hashes[j] != walks[(size_t)ids[job_frame[j]]].want) fl[job_frame[j]] = 1;
+    if ((uint32_t)hashes[j] != walks[(size_t)ids[job_frame[j]]].want)
+      fl[job_frame[j]] = zh_zd::kChecksumMismatch;
   for (size_t k = 0; k < nf; k++) flags[(size_t)ids[k]] = fl[k];
   return ZH_OK;
 }
@@ -295,7 +303,7 @@ int zh_zstd_decode_batch(zh_ctx* ctx, zh_zstd_frame* frames, int64_t n, void* ds
   hipStream_t s = stream_v ? (hipStream_t)stream_v : ctx->stream;
   Stager sg;
   int rc = sg.init(ctx, s);
-  std::vector<uint32_t> flags((size_t)n, 0);  // 1: the host decoder names this frame's verdict
+  std::vector<uint32_t> flags((size_t)n, 0);  // set: zh_zstd_decompress names the verdict
   std::vector<uint8_t> hostbuf;
   double ms = 0;
   // host-decoded frames: zh_zstd_decompress, then one copy
@@ -336,7 +344,7 @@ int zh_zstd_decode_batch(zh_ctx* ctx, zh_zstd_frame* frames, int64_t n, void* ds
     return rc;
   }
   g_last_zdec_ms.store(ms);
-  // flagged frames in batch order: the host decoder's status and text, or its bytes
+  // flagged frames in batch order: zh_zstd_decompress's status and text, or its bytes
   for (int64_t i = 0; i < n; i++) {
     zh_zstd_frame& f = frames[i];
     if (!flags[(size_t)i]) continue;
@@ -350,7 +358,7 @@ int zh_zstd_decode_batch(zh_ctx* ctx, zh_zstd_frame* frames, int64_t n, void* ds
       put_err(err, errlen, msg);
       return hs;
     }
-    // the device refused what the host accepts: the host's bytes, and the frame says so
+    // the wave refused what one lane accepts: the host's bytes, and the frame says so
     if (hipMemcpy((uint8_t*)dst + f.dst_off, hostbuf.data(), (size_t)f.nbytes,
                   hipMemcpyHostToDevice) != hipSuccess) {
       put_err(err, errlen, "zh_zstd_decode_batch: device copy or launch failed");

@@ -11,7 +11,7 @@
 //     size: the literals start at a fixed place and are written while matching), the sequence
 //     count in its 1- or 2-byte form, the modes byte 0 (predefined tables for literal lengths,
 //     offsets and match lengths), then the FSE bitstream: sequences last first, extra bits and
-//     state bits in the reverse of the order decode_block (zh_zstd.cpp) consumes them, the
+//     state bits in the reverse of the order decode_block (zh_zstd_dec.h) consumes them, the
 //     three states, the 1-bit end marker;
 //   * a block whose compressed form would reach its raw size is raw (type 0); neighbouring raw
 //     blocks are merged and cut every 128 KiB, so a frame in which nothing compresses is, byte
@@ -25,7 +25,7 @@
 //   fse_block     serial: walks the list backwards through the three FSE encoders into a
 //                 64-bit accumulator flushed in whole bytes after every field (the widest
 //                 sequence is 16 + 16 + 16 extra bits and 6 + 6 + 5 state bits).
-// The encoding tables (Tables) are derived once on the host, in zh_zstd.cpp, from the Fse::build
+// The encoding tables (Tables) are derived once on the host, in zh_zstd.cpp, from the fse_build
 // the decoder runs on the predefined distributions: for a symbol, the decode-table states that
 // carry it partition the next-state range, so (symbol, next state) -> state is one lookup and
 // encoder and decoder agree by construction.
@@ -59,7 +59,7 @@ struct Tables {
   uint8_t ll_cbits[36], ml_cbits[53];                // extra bits per code
   uint32_t ll_cbase[36], ml_cbase[53];               // first value per code
 };
-// Built once from Fse::build (zh_zstd.cpp).
+// Built once from zh_zd::fse_build (in zh_zstd.cpp).
 const Tables& tables();
 
 ZH_BS_HD uint32_t highbit32(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
