@@ -742,6 +742,61 @@ int zh_zstd_encode_batch(zh_ctx* ctx, zh_zstd_enc_frame* frames, int64_t n,
 double zh_debug_zstd_encode_kernel_ms(void);
 int zh_debug_zstd_xxh64(zh_ctx* ctx, const zh_zstd_enc_frame* frames, int64_t n, uint64_t* out);
 
+/* ---- gzip members written by the library, on the host or on the device ---------------
+ * One member per call / per source, never concatenated members (RFC 1952; header
+ * 1f 8b 08 00 00 00 00 00 00 ff: no name, mtime 0, OS 255).  The content is cut into blocks of
+ * `blocksize` bytes, each compressed on its own (greedy LZ over a 1024-slot table, no match
+ * reaching before the block) into one byte-aligned segment: a fixed-Huffman DEFLATE block
+ * followed by an empty stored block, or, when that is not smaller, a stored block (5 bytes over
+ * raw).  The member ends with the final empty fixed block 03 00, the CRC-32 and the size.  No
+ * dynamic-Huffman blocks: bytes that LZ alone does not shrink are stored.  No member is larger
+ * than 20 + n + 5 * ceil(n / blocksize): the bound.  The bytes are a pure function of (input,
+ * block size): the host call and the batch call give the same member.  The codec's `level` is
+ * not honoured. */
+typedef struct zh_gzip_enc_params {
+  int32_t blocksize;  /* 0: default (16 KiB); below 1 KiB: 1 KiB; above 32 KiB: 32 KiB  */
+} zh_gzip_enc_params;
+
+typedef struct zh_gzip_enc_frame {
+  const void* src;   /* raw bytes: device memory                               */
+  int64_t nbytes;
+  int64_t dst_off;   /* out: place of the member in dst, 16-byte aligned       */
+  int64_t cbytes;    /* out: size of the member                                */
+  int32_t status;    /* out: ZH_OK or this member's error                      */
+} zh_gzip_enc_frame;
+
+/* Host, no device: one member.  dst == NULL: *len = the bound (cap must reach it otherwise). */
+int zh_gzip_compress(const void* src, size_t n, const zh_gzip_enc_params* params, void* dst,
+                     size_t cap, size_t* len, char* err, size_t errlen);
+
+/* CRC-32 (IEEE, the gzip trailer's) with zlib's chaining: zh_crc32(zh_crc32(0, a), b) is the
+ * CRC of a || b; data == NULL: 0. */
+uint32_t zh_crc32(uint32_t crc, const void* data, size_t len);
+
+/* Host memory a batch needs for its members: the sum of the bounds, each rounded up to 16
+ * bytes; or -zh_status. */
+int64_t zh_gzip_encode_bound(const zh_gzip_enc_frame* frames, int64_t n,
+                             const zh_gzip_enc_params* params);
+
+/* Sources in device memory, at any byte alignment; the members arrive in host memory dst
+ * (dstcap >= the bound) at dst_off, cbytes long.  One kernel hashes the whole batch (one
+ * workgroup per 64 KiB span; the spans' CRCs are combined on the host), then per slab one
+ * kernel matches (one wavefront per block), a second codes literals and matches (one wavefront
+ * per block), a third lays the members out; they leave through the context's page-locked ring.
+ * Runs on `stream` (NULL: the context's) and waits.  Slabs of at most 128 MiB of raw bytes (a
+ * larger source is its own slab) bound the device memory of a call. */
+int zh_gzip_encode_batch(zh_ctx* ctx, zh_gzip_enc_frame* frames, int64_t n,
+                         const zh_gzip_enc_params* params, void* dst, int64_t dstcap,
+                         void* stream, char* err, size_t errlen);
+
+/* Diagnostics: milliseconds the kernels of the last successful zh_gzip_encode_batch took, by
+ * device events, summed over its slabs (-1: none yet), and the same per kernel into out[4]:
+ * match, coder, CRC-32, gather; CRC-32 of n device buffers by the batch's hash kernel and the
+ * host combination into out[n] (host). */
+double zh_debug_gzip_encode_kernel_ms(void);
+void zh_debug_gzip_encode_kernel_parts_ms(double out[4]);
+int zh_debug_gzip_crc32(zh_ctx* ctx, const zh_gzip_enc_frame* frames, int64_t n, uint32_t* out);
+
 /* ---- zstd frames decoded on the device, a batch at a time -----------------------------
  * The read side of the batch above, in the shape of zh_blosc_decode_batch.  A stored chunk that
  * is exactly one zstd frame with a Frame_Content_Size, no dictionary and a block chain that ends

@@ -1,0 +1,624 @@
+// zh_gzip_enc_kernels.hip — gzip members written on the device, a batch at a time
+// (zh_gzip_encode_bound / zh_gzip_encode_batch); the member and the block encoder are
+// zh_gzip_enc.h, the host form zh_gzip_compress (zh_gzip.cpp) is the byte-for-byte oracle.
+//
+// The raw bytes are in device memory (zh_array_write's chunk buffers); the members go to the host.
+//   gzip_crc32_kernel   one workgroup per (source, 64 KiB span), one launch for the whole batch
+//           ahead of its slabs.  The span's whole 256-byte pieces are loaded into LDS as aligned
+//           words shifted into place (any source alignment), 65 words apart so that the threads'
+//           reads spread over the banks; thread t hashes one piece bytewise through a 256-entry
+//           table in LDS; the pieces sit at the end of the thread row (a register that starts at
+//           0 ignores leading zeros), so a tree of 8 steps folds them with x^(8 * 256 * 2^k);
+//           the last thread adds the span's tail.  The host folds the spans of a source
+//           (zh_gz::crc_append) and finishes the register (zh_gz::crc_finish).
+//   gzip_match_kernel<CAP, WAVES>   one wave per block of at most CAP bytes (16 or 32 KiB by the
+//           batch's block size), WAVES blocks per workgroup: the wave loads its block into its
+//           part of LDS, next to its hash table, and runs zh_gz::match_block over WaveLanes;
+//           the records go to the block's part of the list in global memory.  No barrier.
+//   gzip_deflate_kernel<CAP, WAVES>   one wave per block, the wave form of
+//           zh_gz::deflate_block: the block again in LDS, next to a zeroed window of its size;
+//           the records are read 64 at a time; the lanes take 64 consecutive literals of a
+//           record (or the pieces of its match), compute (bits, count) with the functions the
+//           host form uses, a wave scan of the counts gives each lane its bit offset, and the
+//           bits are OR-ed into the window (deterministic: OR commutes).  The finished segment
+//           goes to the block's region of the scratch buffer in whole words; its size (or the
+//           stored size) goes to a table.  The kernel boundary orders the records.  The form
+//           with one thread per block that was built first took 113 ms where the match kernel
+//           took 5.9 ms (DESIGN.md "Gzip members encoded on the device").
+//   host    one small copy brings the size table back; a prefix sum lays the members out and
+//           builds the copy jobs;
+//   blosc_gather_kernel (zh_enc_device.h)   one workgroup per job: headers and endings from the
+//           uploaded table, fixed segments from the scratch, stored segments from the source
+//           behind their 5 header bytes;
+//   D2H     the compact buffer through the context's page-locked out ring into host memory.
+// Slabs of at most kSlabBytes of raw input bound the device memory: per slab the scratch (the raw
+// size and up to 23 bytes a block), the records (1.5 x), the compact members and the small tables.
+// Every job and block row is built on the host from validated sizes; the size table is checked
+// against the block sizes before it lays anything out.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <vector>
+
+#include "zh_ctx.h"
+#include "zh_enc_device.h"
+#include "zh_gzip_enc.h"
+
+namespace {
+
+constexpr int64_t kSlabBytes = (int64_t)128 << 20;
+constexpr uint32_t kSpan = 64u << 10;  // bytes per workgroup of the CRC kernel
+constexpr uint32_t kPiece = 256;       // bytes per thread
+constexpr uint32_t kPieceWords = kPiece / 4, kPieceStride = kPieceWords + 1;
+static_assert(kSpan == kThreads * kPiece, "one piece per thread");
+constexpr size_t kMetaStride = 32;  // per member: the header at 0, the ending and trailer at 10
+
+struct GBlock {
+  uint64_t src;  // device address of the raw block
+  uint64_t out;  // offset of the block's region in the scratch buffer
+  uint64_t seq;  // offset of the block's records in the list, in uint16
+  uint32_t size, pad;
+};
+struct CrcJob {
+  uint64_t src;
+  uint32_t len, pad;  // len <= kSpan
+};
+
+// The block into the wave's part of LDS: 16 bytes a lane where source and block agree on it.
+__device__ inline void load_block(uint8_t* blk, const uint8_t* __restrict__ src, uint32_t size,
+                                  uint32_t lane) {
+  const uint32_t al = (uint32_t)(((uintptr_t)src) & 15);
+  for (uint32_t q0 = lane * 16; q0 < size; q0 += 64 * 16) {
+    const uint32_t cnt = size - q0 < 16u ? size - q0 : 16u;
+    if (cnt == 16 && al == 0) {
+      *(uint4*)(blk + q0) = *(const uint4*)(src + q0);
+    } else if (cnt == 16 && (al & 3) == 0) {  // inner chunks behind a shard's index
+      const uint32_t* s4 = (const uint32_t*)(src + q0);
+      *(uint4*)(blk + q0) = make_uint4(s4[0], s4[1], s4[2], s4[3]);
+    } else {
+      for (uint32_t i = 0; i < cnt; i++) blk[q0 + i] = src[q0 + i];
+    }
+  }
+}
+
+template <uint32_t CAP, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void gzip_match_kernel(
+    const GBlock* __restrict__ blocks, uint32_t nblocks, uint16_t* __restrict__ seqs,
+    uint32_t* __restrict__ info) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[WAVES][CAP];
+  __shared__ uint32_t tables[WAVES][zh_lz::kHashSize];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t k = blockIdx.x * WAVES + wave;
+  if (k >= nblocks) return;  // the whole wave: the kernel has no barrier
+  const GBlock b = blocks[k];
+  if (b.size > CAP) return;  // never: the host picks CAP from the block size
+  uint8_t* blk = lds[wave];
+  load_block(blk, (const uint8_t*)b.src, b.size, lane);
+  WaveLanes::order();
+  WaveLanes w;
+  w.lane = lane;
+  w.h = 0;
+  w.wide = true;
+  uint32_t covered = 0;
+  const uint32_t ns = zh_gz::match_block(blk, b.size, seqs + b.seq, tables[wave], w, &covered);
+  if (lane == 0) {
+    info[2 * k] = ns;
+    info[2 * k + 1] = covered;
+  }
+}
+
+// The wave form of zh_gz::deflate_block.  The bit position of a symbol is a prefix sum of code
+// lengths: the lanes take 64 consecutive literals (or the pieces of one long match), compute
+// (bits, count), a wave scan gives each lane its offset, and the bits are OR-ed into the block's
+// zeroed window in LDS (OR commutes: the window does not depend on the order).  A literal is 8
+// or 9 bits, so its scan is two ballots and two population counts; a match of one piece needs
+// none; only the pieces of a match longer than 258 go through the shuffle scan.
+struct WaveCoder {
+  uint32_t* win;
+  uint32_t lane, bitpos, limit;  // limit: the symbols' bits may reach it, not pass it
+  bool over = false;
+
+  __device__ void bits(uint32_t at, uint32_t v, uint32_t nb) {  // nb <= 32
+    const uint64_t x = (uint64_t)v << (at & 31u);
+    atomicOr(&win[at >> 5], (uint32_t)x);
+    if ((at & 31u) + nb > 32) atomicOr(&win[(at >> 5) + 1], (uint32_t)(x >> 32));
+  }
+  // up to 64 literals in lane order: 8 bits, 9 where `nine`
+  __device__ void literals(uint32_t v, bool act, bool nine) {
+    const unsigned long long ma = __ballot(act), m9 = __ballot(act && nine);
+    const uint32_t total = 8 * (uint32_t)__popcll(ma) + (uint32_t)__popcll(m9);
+    if (bitpos + total > limit) {
+      over = true;
+      return;
+    }
+    const unsigned long long lower = (1ull << lane) - 1;
+    if (act)
+      bits(bitpos + 8 * (uint32_t)__popcll(ma & lower) + (uint32_t)__popcll(m9 & lower), v,
+           nine ? 9u : 8u);
+    bitpos += total;
+  }
+  // one symbol, the same in every lane
+  __device__ void one(uint32_t v, uint32_t nb) {
+    if (bitpos + nb > limit) {
+      over = true;
+      return;
+    }
+    if (lane == 0) bits(bitpos, v, nb);
+    bitpos += nb;
+  }
+  // every lane's (v, nb), nb == 0 for a lane without a symbol, in lane order
+  __device__ void put(uint32_t v, uint32_t nb) {
+    uint32_t incl = nb;
+    for (int d = 1; d < 64; d *= 2) {
+      const uint32_t y = (uint32_t)__shfl_up((int)incl, d);
+      if (lane >= (uint32_t)d) incl += y;
+    }
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    if (bitpos + total > limit) {
+      over = true;
+      return;
+    }
+    if (nb) bits(bitpos + incl - nb, v, nb);
+    bitpos += total;
+  }
+};
+
+template <uint32_t CAP, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void gzip_deflate_kernel(
+    const GBlock* __restrict__ blocks, uint32_t nblocks, uint8_t* __restrict__ scratch,
+    const uint16_t* __restrict__ seqs, const uint32_t* __restrict__ info,
+    uint32_t* __restrict__ csize) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[WAVES][CAP];
+  __shared__ uint32_t wins[WAVES][CAP / 4 + 4];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t k = blockIdx.x * WAVES + wave;
+  if (k >= nblocks) return;  // the whole wave: the kernel has no barrier
+  const GBlock b = blocks[k];
+  const uint32_t n = b.size, stored = n + zh_gz::kStoredOver;
+  const uint32_t ns = info[2 * k], covered = info[2 * k + 1];
+  // the tests of zh_gz::deflate_block before it codes anything, and the list's room
+  if (n > CAP || ns > n / zh_lz::kMinMatch || covered > n ||
+      (8 * (n - covered) + 12 * ns + 13 + 7) / 8 + 4 >= stored) {
+    if (lane == 0) csize[k] = stored;
+    return;
+  }
+  uint8_t* blk = lds[wave];
+  uint32_t* win = wins[wave];
+  load_block(blk, (const uint8_t*)b.src, n, lane);
+  const uint32_t nwin = (n + 4) / 4 + 2;  // n + 4 bytes and the word a symbol may reach into
+  for (uint32_t i = lane; i < nwin; i += 64) win[i] = i == 0 ? 2u : 0u;  // BFINAL 0, BTYPE 01
+  WaveLanes::order();
+  // a segment of more than n + 4 bytes is stored: end of block, marker bits, 4 marker bytes
+  WaveCoder c{win, lane, 3, 8 * n - 10};
+  const uint16_t* __restrict__ sq = seqs + b.seq;
+  uint32_t pos = 0;
+  for (uint32_t k0 = 0; k0 <= ns && !c.over; k0 += 64) {  // record ns: the literals at the end
+    uint32_t r_lit = 0, r_ml = 0, r_off = 0;
+    if (k0 + lane < ns) {
+      r_lit = sq[3 * (k0 + lane)];
+      r_ml = sq[3 * (k0 + lane) + 1];
+      r_off = sq[3 * (k0 + lane) + 2];
+    }
+    const uint32_t cnt = ns + 1 - k0 < 64u ? ns + 1 - k0 : 64u;
+    for (uint32_t j = 0; j < cnt && !c.over; j++) {
+      const bool last = k0 + j == ns;
+      const uint32_t lit = last ? n - pos : (uint32_t)__builtin_amdgcn_readlane((int)r_lit, j);
+      const uint32_t ml = (uint32_t)__builtin_amdgcn_readlane((int)r_ml, j);
+      const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)r_off, j);
+      if (lit > n - pos) {  // never: the records partition the block
+        c.over = true;
+        break;
+      }
+      for (uint32_t i0 = 0; i0 < lit && !c.over; i0 += 64) {
+        const bool act = i0 + lane < lit;
+        uint32_t v = 0, nb = 0;
+        if (act) v = zh_gz::lit_bits(blk[pos + i0 + lane], &nb);
+        c.literals(v, act, nb == 9);
+      }
+      pos += lit;
+      if (last || c.over) break;
+      if (ml > n - pos || off == 0 || off > pos) {  // never
+        c.over = true;
+        break;
+      }
+      const uint32_t np = zh_gz::piece_count(ml);
+      if (np == 1) {
+        uint32_t nb;
+        const uint32_t v = zh_gz::match_bits(ml, off, &nb);
+        c.one(v, nb);
+      }
+      for (uint32_t p0 = 0; np > 1 && p0 < np && !c.over; p0 += 64) {
+        uint32_t v = 0, nb = 0;
+        if (p0 + lane < np) v = zh_gz::match_bits(zh_gz::piece_len(ml, p0 + lane), off, &nb);
+        c.put(v, nb);
+      }
+      pos += ml;
+    }
+  }
+  if (c.over) {
+    if (lane == 0) csize[k] = stored;
+    return;
+  }
+  const uint32_t bytes = (c.bitpos + 10 + 7) / 8;  // end of block, marker bits, zero bits
+  if (lane == 0) {
+    c.bits(8 * (bytes + 2), 0xFFFFu, 16);  // LEN 0, NLEN ffff
+    csize[k] = bytes + 4;
+  }
+  WaveLanes::order();
+  uint32_t* __restrict__ out = (uint32_t*)(scratch + b.out);  // 16-byte aligned, size + 8 long
+  for (uint32_t i = lane; i < (bytes + 4 + 3) / 4; i += 64) out[i] = win[i];
+}
+
+__global__ __launch_bounds__(kThreads) void gzip_crc32_kernel(const CrcJob* __restrict__ jobs,
+                                                              uint32_t x_piece,
+                                                              uint32_t* __restrict__ out) {
+  __shared__ uint32_t tab[256];
+  __shared__ uint32_t red[kThreads];
+  __shared__ uint32_t words[kThreads * kPieceStride];
+  const uint32_t t = threadIdx.x;
+  tab[t] = zh_gz::crc_table_entry(t);
+  const CrcJob job = jobs[blockIdx.x];
+  const uint8_t* __restrict__ src = (const uint8_t*)job.src;
+  const uint32_t len = job.len < kSpan ? job.len : kSpan;
+  const uint32_t nfull = len / kPiece, nw = nfull * kPieceWords;
+  const uint32_t sh = (uint32_t)(((uintptr_t)src) & 3);
+  // aligned words; when sh != 0 the word behind holds the last byte of word j, inside the span
+  const uint32_t* __restrict__ s4 = (const uint32_t*)(src - sh);
+  for (uint32_t j = t; j < nw; j += kThreads) {
+    const uint32_t x0 = s4[j];
+    const uint32_t x1 = sh ? s4[j + 1] : 0u;
+    words[(j / kPieceWords) * kPieceStride + j % kPieceWords] =
+        sh ? __builtin_amdgcn_alignbyte(x1, x0, sh) : x0;
+  }
+  __syncthreads();
+  const uint32_t first = kThreads - nfull;  // the pieces end the row: leading zeros are free
+  uint32_t r = 0;
+  if (t >= first) {
+    const uint32_t* w = words + (t - first) * kPieceStride;
+    for (uint32_t i = 0; i < kPieceWords; i++) {
+      r ^= w[i];
+      for (int q = 0; q < 4; q++) r = tab[r & 255u] ^ (r >> 8);
+    }
+  }
+  red[t] = r;
+  __syncthreads();
+  uint32_t m = x_piece;  // x^(8 * kPiece * step)
+  for (uint32_t step = 1; step < kThreads; step *= 2) {
+    const uint32_t mask = 2 * step - 1;
+    if ((t & mask) == mask) red[t] = zh_gz::crc_append(red[t - step], red[t], m);
+    m = zh_gz::mulmod(m, m);
+    __syncthreads();
+  }
+  if (t == kThreads - 1) {
+    r = red[t];
+    for (uint32_t q = nfull * kPiece; q < len; q++) r = tab[(r ^ src[q]) & 255u] ^ (r >> 8);
+    out[blockIdx.x] = r;
+  }
+}
+
+std::atomic<double> g_last_genc_ms{-1.0};
+std::atomic<double> g_last_genc_part[4] = {{-1.0}, {-1.0}, {-1.0}, {-1.0}};
+enum Part { kMatch = 0, kCoder = 1, kCrc = 2, kGather = 3 };
+
+void launch_match(uint32_t B, hipStream_t s, const GBlock* blocks, uint32_t nblocks,
+                  uint16_t* seqs, uint32_t* info) {
+  if (B <= (16u << 10)) {
+    hipLaunchKernelGGL((gzip_match_kernel<(16u << 10), 4>), dim3((nblocks + 3) / 4), dim3(256), 0,
+                       s, blocks, nblocks, seqs, info);
+  } else {
+    hipLaunchKernelGGL((gzip_match_kernel<zh_gz::kMaxBlock, 4>), dim3((nblocks + 3) / 4),
+                       dim3(256), 0, s, blocks, nblocks, seqs, info);
+  }
+}
+
+void launch_deflate(uint32_t B, hipStream_t s, const GBlock* blocks, uint32_t nblocks,
+                    uint8_t* scratch, const uint16_t* seqs, const uint32_t* info,
+                    uint32_t* csize) {
+  if (B <= (16u << 10)) {
+    hipLaunchKernelGGL((gzip_deflate_kernel<(16u << 10), 4>), dim3((nblocks + 3) / 4), dim3(256),
+                       0, s, blocks, nblocks, scratch, seqs, info, csize);
+  } else {
+    hipLaunchKernelGGL((gzip_deflate_kernel<zh_gz::kMaxBlock, 2>), dim3((nblocks + 1) / 2),
+                       dim3(128), 0, s, blocks, nblocks, scratch, seqs, info, csize);
+  }
+}
+
+struct MemberPlan {
+  int64_t first_block = 0, nblocks = 0;  // within the slab
+};
+
+// One slab [f0, f1) of the batch; crcs: the batch's, finished; *pos: the running offset in dst.
+int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, const uint32_t* crcs,
+                zh_gzip_enc_frame* frames, int64_t f0, int64_t f1, const zh_gz::Params& P,
+                uint8_t* dst, int64_t* pos, double* part_ms) {
+  const int64_t nf = f1 - f0;
+  std::vector<MemberPlan> plan((size_t)nf);
+  std::vector<GBlock> blocks;
+  int64_t scratch_total = 0, seq_total = 0, compact_cap = 0, njobs_cap = 0;
+  for (int64_t i = f0; i < f1; i++) {
+    MemberPlan& mp = plan[(size_t)(i - f0)];
+    const size_t n = (size_t)frames[i].nbytes;
+    mp.first_block = (int64_t)blocks.size();
+    mp.nblocks = (int64_t)zh_gz::block_count(n, P.B);
+    for (int64_t k = 0; k < mp.nblocks; k++) {
+      GBlock b;
+      b.size = zh_gz::block_size(n, P.B, (size_t)k);
+      b.src = (uint64_t)(uintptr_t)frames[i].src + (uint64_t)k * P.B;
+      b.out = (uint64_t)scratch_total;
+      b.seq = (uint64_t)seq_total;
+      b.pad = 0;
+      blocks.push_back(b);
+      scratch_total += up((int64_t)b.size + 8, 16);  // size + 4 bytes, stored as whole words
+      seq_total += up(3 * (int64_t)(b.size / 4) + 3, 8);
+    }
+    compact_cap += up((int64_t)zh_gz::member_bound(n, P.B), 16);
+    njobs_cap += 2 + 2 * mp.nblocks;
+  }
+  if (blocks.size() > (size_t)zh::kIntMax || njobs_cap > zh::kIntMax) return ZH_EINVAL;
+  const size_t nb = blocks.size();
+
+  // device memory: [blocks | info | csize | jobs | meta | seqs | scratch | compact]
+  const size_t o_blocks = 0;
+  const size_t o_info = o_blocks + (size_t)up((int64_t)(nb * sizeof(GBlock)), 256);
+  const size_t o_cs = o_info + (size_t)up((int64_t)nb * 8, 256);
+  const size_t o_jobs = o_cs + (size_t)up((int64_t)nb * 4, 256);
+  const size_t o_meta = o_jobs + (size_t)up(njobs_cap * (int64_t)sizeof(GatherJob), 256);
+  const size_t o_seq = o_meta + (size_t)up(nf * (int64_t)kMetaStride, 256);
+  const size_t o_scratch = o_seq + (size_t)up(seq_total * 2, 256);
+  const size_t o_compact = o_scratch + (size_t)up(scratch_total, 256);
+  const size_t need = o_compact + (size_t)compact_cap + 256;
+  void* dmem = nullptr;
+  size_t got = 0;
+  if (zh::ctx_alloc(ctx, need, &dmem, &got) != hipSuccess) {
+    (void)hipGetLastError();
+    return ZH_ENOMEM;
+  }
+  uint8_t* d8 = (uint8_t*)dmem;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (auto& e : ev) (void)hipEventCreate(&e);
+  const bool timed = ev[0] && ev[1] && ev[2] && ev[3] && ev[4];
+  int rc = ZH_OK;
+  std::vector<uint32_t> cs(nb, 0);
+  if (nb && !ring.h2d(d8 + o_blocks, (const uint8_t*)blocks.data(), nb * sizeof(GBlock)))
+    rc = ZH_EHIP;
+  if (rc == ZH_OK) {
+    if (timed) (void)hipEventRecord(ev[0], s);
+    if (nb)
+      launch_match(P.B, s, (const GBlock*)(d8 + o_blocks), (uint32_t)nb, (uint16_t*)(d8 + o_seq),
+                   (uint32_t*)(d8 + o_info));
+    if (timed) (void)hipEventRecord(ev[1], s);
+    if (nb)
+      launch_deflate(P.B, s, (const GBlock*)(d8 + o_blocks), (uint32_t)nb, d8 + o_scratch,
+                     (const uint16_t*)(d8 + o_seq), (const uint32_t*)(d8 + o_info),
+                     (uint32_t*)(d8 + o_cs));
+    if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
+    if (timed) (void)hipEventRecord(ev[2], s);
+  }
+  if (rc == ZH_OK && nb && !ring.d2h((uint8_t*)cs.data(), d8 + o_cs, nb * 4)) rc = ZH_EHIP;
+  // the table lays out device copies: nothing in it may pass its block's stored size
+  for (size_t k = 0; k < nb && rc == ZH_OK; k++)
+    if (cs[k] < zh_gz::kMinSegment || cs[k] > blocks[k].size + zh_gz::kStoredOver) rc = ZH_EHIP;
+
+  // layout: the members side by side in the compact buffer, each 16-byte aligned
+  std::vector<GatherJob> jobs;
+  std::vector<uint8_t> meta;
+  int64_t cpos = 0;
+  if (rc == ZH_OK) {
+    meta.resize((size_t)nf * kMetaStride, 0);
+    jobs.reserve((size_t)njobs_cap);
+    const uint64_t d_meta = (uint64_t)(uintptr_t)(d8 + o_meta);
+    const uint64_t d_scratch = (uint64_t)(uintptr_t)(d8 + o_scratch);
+    const uint64_t d_compact = (uint64_t)(uintptr_t)(d8 + o_compact);
+    for (int64_t i = f0; i < f1; i++) {
+      const MemberPlan& mp = plan[(size_t)(i - f0)];
+      const size_t n = (size_t)frames[i].nbytes;
+      const size_t m0 = (size_t)(i - f0) * kMetaStride;
+      zh_gz::put_header(meta.data() + m0);
+      zh_gz::put_ending(meta.data() + m0 + zh_gz::kHeader, crcs[i], n);
+      const uint64_t fbase = d_compact + (uint64_t)cpos;
+      uint64_t d = fbase;
+      jobs.push_back({d_meta + m0, d, (uint32_t)zh_gz::kHeader, 0, 0, 0});
+      d += zh_gz::kHeader;
+      for (int64_t k = 0; k < mp.nblocks; k++) {
+        const GBlock& b = blocks[(size_t)(mp.first_block + k)];
+        const uint32_t size = cs[(size_t)(mp.first_block + k)];
+        if (size == b.size + zh_gz::kStoredOver) {  // 00, then LEN NLEN and the bytes
+          jobs.push_back({d_meta + m0, d, 0, 0, 1, 0});
+          jobs.push_back({b.src, d + 1, b.size, zh_gz::stored_word(b.size), 4, 0});
+        } else {
+          jobs.push_back({d_scratch + b.out, d, size, 0, 0, 0});
+        }
+        d += size;
+      }
+      jobs.push_back({d_meta + m0 + zh_gz::kHeader, d,
+                      (uint32_t)(zh_gz::kEnding + zh_gz::kTrailer), 0, 0, 0});
+      d += zh_gz::kEnding + zh_gz::kTrailer;
+      const size_t total = (size_t)(d - fbase);
+      if (total > zh_gz::member_bound(n, P.B)) rc = ZH_EHIP;  // layout and bound disagree
+      frames[i].dst_off = *pos + cpos;
+      frames[i].cbytes = (int64_t)total;
+      frames[i].status = ZH_OK;
+      cpos += up((int64_t)total, 16);
+    }
+    if ((int64_t)jobs.size() > njobs_cap || cpos > compact_cap) rc = ZH_EHIP;  // the allocation
+  }
+  if (rc == ZH_OK && !jobs.empty()) {
+    if (!ring.h2d(d8 + o_jobs, (const uint8_t*)jobs.data(), jobs.size() * sizeof(GatherJob)) ||
+        !ring.h2d(d8 + o_meta, meta.data(), meta.size()))
+      rc = ZH_EHIP;
+    if (rc == ZH_OK) {
+      if (timed) (void)hipEventRecord(ev[3], s);
+      hipLaunchKernelGGL(blosc_gather_kernel, dim3((unsigned)jobs.size()), dim3(kThreads), 0, s,
+                         (const GatherJob*)(d8 + o_jobs));
+      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
+      if (timed) (void)hipEventRecord(ev[4], s);
+    }
+    if (rc == ZH_OK && !ring.d2h(dst + *pos, d8 + o_compact, (size_t)cpos)) rc = ZH_EHIP;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
+  if (rc == ZH_OK && timed && !jobs.empty()) {
+    float a = 0, b = 0, c = 0;
+    if (hipEventElapsedTime(&a, ev[0], ev[1]) != hipSuccess) a = 0;
+    if (hipEventElapsedTime(&b, ev[1], ev[2]) != hipSuccess) b = 0;
+    if (hipEventElapsedTime(&c, ev[3], ev[4]) != hipSuccess) c = 0;
+    part_ms[kMatch] += (double)a;
+    part_ms[kCoder] += (double)b;
+    part_ms[kGather] += (double)c;
+  }
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  zh::ctx_release(ctx, dmem, got);
+  if (rc == ZH_OK) *pos += cpos;
+  return rc;
+}
+
+// CRC-32 of every source of the batch into crcs[n] (host): one launch over all spans, the spans
+// folded on the host.
+int crc_frames(zh_ctx* ctx, hipStream_t s, Ring& ring, const zh_gzip_enc_frame* frames, int64_t n,
+               uint32_t* crcs, double* kernel_ms) {
+  std::vector<CrcJob> cj;
+  for (int64_t i = 0; i < n; i++) {
+    const uint64_t nbytes = (uint64_t)frames[i].nbytes;
+    for (uint64_t o = 0; o < nbytes; o += kSpan)
+      cj.push_back({(uint64_t)(uintptr_t)frames[i].src + o,
+                    (uint32_t)std::min<uint64_t>(kSpan, nbytes - o), 0});
+  }
+  if (cj.size() > (size_t)zh::kIntMax) return ZH_EINVAL;
+  std::vector<uint32_t> raw(cj.size(), 0);
+  int rc = ZH_OK;
+  if (!cj.empty()) {
+    void* dmem = nullptr;
+    size_t got = 0;
+    const size_t o_out = (size_t)up((int64_t)(cj.size() * sizeof(CrcJob)), 256);
+    if (zh::ctx_alloc(ctx, o_out + cj.size() * 4, &dmem, &got) != hipSuccess) {
+      (void)hipGetLastError();
+      return ZH_ENOMEM;
+    }
+    uint8_t* d8 = (uint8_t*)dmem;
+    if (!ring.h2d(d8, (const uint8_t*)cj.data(), cj.size() * sizeof(CrcJob))) rc = ZH_EHIP;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    for (auto& e : ev) (void)hipEventCreate(&e);
+    if (rc == ZH_OK) {
+      if (ev[0]) (void)hipEventRecord(ev[0], s);
+      hipLaunchKernelGGL(gzip_crc32_kernel, dim3((unsigned)cj.size()), dim3(kThreads), 0, s,
+                         (const CrcJob*)d8, zh_gz::xpow8(kPiece), (uint32_t*)(d8 + o_out));
+      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
+      if (ev[1]) (void)hipEventRecord(ev[1], s);
+    }
+    if (rc == ZH_OK && !ring.d2h((uint8_t*)raw.data(), d8 + o_out, cj.size() * 4)) rc = ZH_EHIP;
+    if (hipStreamSynchronize(s) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
+    float ms = 0;
+    if (rc == ZH_OK && ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+      *kernel_ms += (double)ms;
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    zh::ctx_release(ctx, dmem, got);
+    if (rc != ZH_OK) return rc;
+  }
+  const uint32_t x_span = zh_gz::xpow8(kSpan);
+  size_t j = 0;
+  for (int64_t i = 0; i < n; i++) {
+    const uint64_t nbytes = (uint64_t)frames[i].nbytes;
+    uint32_t r = 0;
+    for (uint64_t o = 0; o < nbytes; o += kSpan, j++)
+      r = zh_gz::crc_append(r, raw[j], cj[j].len == kSpan ? x_span : zh_gz::xpow8(cj[j].len));
+    crcs[i] = zh_gz::crc_finish(r, nbytes);
+  }
+  return ZH_OK;
+}
+
+bool sources_ok(const zh_gzip_enc_frame* frames, int64_t n) {
+  if (n < 0 || (n > 0 && !frames)) return false;
+  for (int64_t i = 0; i < n; i++)
+    if (frames[i].nbytes < 0 || (frames[i].nbytes > 0 && !frames[i].src)) return false;
+  return true;
+}
+
+int64_t bound_of(const zh_gzip_enc_frame* frames, int64_t n, const zh_gzip_enc_params* prm) {
+  zh_gz::Params P;
+  if (!sources_ok(frames, n) || !zh_gz::read_params(prm, &P)) return -(int64_t)ZH_EINVAL;
+  int64_t total = 0;
+  for (int64_t i = 0; i < n; i++)
+    total += up((int64_t)zh_gz::member_bound((size_t)frames[i].nbytes, P.B), 16);
+  return total;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t zh_gzip_encode_bound(const zh_gzip_enc_frame* frames, int64_t n,
+                             const zh_gzip_enc_params* params) {
+  return bound_of(frames, n, params);
+}
+
+double zh_debug_gzip_encode_kernel_ms(void) { return g_last_genc_ms.load(); }
+
+void zh_debug_gzip_encode_kernel_parts_ms(double out[4]) {
+  for (int k = 0; k < 4; k++) out[k] = g_last_genc_part[k].load();
+}
+
+int zh_gzip_encode_batch(zh_ctx* ctx, zh_gzip_enc_frame* frames, int64_t n,
+                         const zh_gzip_enc_params* params, void* dst, int64_t dstcap,
+                         void* stream_v, char* err, size_t errlen) {
+  if (!ctx) return ZH_EINVAL;
+  const int64_t bound = bound_of(frames, n, params);
+  if (bound < 0) {
+    for (int64_t i = 0; i < n && frames; i++) frames[i].status = ZH_EINVAL;
+    put_err(err, errlen, "gzip encode: blocksize >= 0, sizes >= 0");
+    return ZH_EINVAL;
+  }
+  if (bound > dstcap || (bound > 0 && !dst)) {
+    put_err(err, errlen, "zh_gzip_encode_batch: destination smaller than zh_gzip_encode_bound");
+    return ZH_EINVAL;
+  }
+  if (n == 0) return ZH_OK;
+  zh_gz::Params P;
+  (void)zh_gz::read_params(params, &P);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = stream_v ? (hipStream_t)stream_v : ctx->stream;
+  Ring ring;
+  int rc = ring.init(ctx, s);
+  int64_t pos = 0;
+  double part[4] = {0, 0, 0, 0};
+  std::vector<uint32_t> crcs;
+  if (rc == ZH_OK && n > zh::kIntMax) rc = ZH_EINVAL;
+  if (rc == ZH_OK) {
+    crcs.assign((size_t)n, 0);
+    rc = crc_frames(ctx, s, ring, frames, n, crcs.data(), &part[kCrc]);
+  }
+  for (int64_t f0 = 0; f0 < n && rc == ZH_OK;) {
+    int64_t f1 = f0, raw = 0;
+    do raw += frames[f1++].nbytes;
+    while (f1 < n && raw + frames[f1].nbytes <= kSlabBytes);
+    rc = encode_slab(ctx, s, ring, crcs.data(), frames, f0, f1, P, (uint8_t*)dst, &pos, part);
+    f0 = f1;
+  }
+  if (rc != ZH_OK) {
+    (void)hipGetLastError();
+    put_err(err, errlen, rc == ZH_ENOMEM   ? "zh_gzip_encode_batch: out of device memory"
+                         : rc == ZH_EINVAL ? "zh_gzip_encode_batch: too many blocks in a slab"
+                                           : "zh_gzip_encode_batch: device copy or launch failed");
+    return rc;
+  }
+  for (int k = 0; k < 4; k++) g_last_genc_part[k].store(part[k]);
+  g_last_genc_ms.store(part[0] + part[1] + part[2] + part[3]);
+  return ZH_OK;
+}
+
+int zh_debug_gzip_crc32(zh_ctx* ctx, const zh_gzip_enc_frame* frames, int64_t n, uint32_t* out) {
+  if (!ctx || n > zh::kIntMax || !sources_ok(frames, n) || (n > 0 && !out)) return ZH_EINVAL;
+  if (n == 0) return ZH_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  (void)hipSetDevice(ctx->device);
+  Ring ring;
+  const int rc = ring.init(ctx, ctx->stream);
+  if (rc != ZH_OK) return rc;
+  double ms = 0;
+  return crc_frames(ctx, ctx->stream, ring, frames, n, out, &ms);
+}
+
+}  // extern "C"

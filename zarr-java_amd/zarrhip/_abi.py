@@ -120,6 +120,17 @@ class zh_zstd_enc_frame(C.Structure):
                 ("cbytes", C.c_int64), ("status", C.c_int32)]
 
 
+class zh_gzip_enc_params(C.Structure):
+    """How gzip members are written (zarrhip.h zh_gzip_enc_params)."""
+    _fields_ = [("blocksize", C.c_int32)]
+
+
+class zh_gzip_enc_frame(C.Structure):
+    """One member of a batched device gzip encode (zarrhip.h zh_gzip_enc_frame)."""
+    _fields_ = [("src", C.c_void_p), ("nbytes", C.c_int64), ("dst_off", C.c_int64),
+                ("cbytes", C.c_int64), ("status", C.c_int32)]
+
+
 class zh_file_store(C.Structure):
     """A FilesystemStore as the file reads name it (zarrhip.h zh_file_store)."""
     _fields_ = [("root", C.c_char_p), ("name", C.c_char_p)]

@@ -115,6 +115,16 @@ _SIGS = {
                                        C.POINTER(A.zh_zstd_enc_params), P, I64, P, CH, SZ]),
     "zh_debug_zstd_encode_kernel_ms": (C.c_double, []),
     "zh_debug_zstd_xxh64": (C.c_int, [P, C.POINTER(A.zh_zstd_enc_frame), I64, C.POINTER(U64)]),
+    "zh_gzip_compress": (C.c_int, [P, SZ, C.POINTER(A.zh_gzip_enc_params), P, SZ, C.POINTER(SZ),
+                                   CH, SZ]),
+    "zh_crc32": (U32, [U32, P, SZ]),
+    "zh_gzip_encode_bound": (I64, [C.POINTER(A.zh_gzip_enc_frame), I64,
+                                   C.POINTER(A.zh_gzip_enc_params)]),
+    "zh_gzip_encode_batch": (C.c_int, [P, C.POINTER(A.zh_gzip_enc_frame), I64,
+                                       C.POINTER(A.zh_gzip_enc_params), P, I64, P, CH, SZ]),
+    "zh_debug_gzip_encode_kernel_ms": (C.c_double, []),
+    "zh_debug_gzip_encode_kernel_parts_ms": (None, [C.POINTER(C.c_double)]),
+    "zh_debug_gzip_crc32": (C.c_int, [P, C.POINTER(A.zh_gzip_enc_frame), I64, C.POINTER(U32)]),
     "zh_zstd_batch_plan": (I64, [C.POINTER(A.zh_zstd_frame), I64, CH, SZ]),
     "zh_zstd_decode_batch": (C.c_int, [P, C.POINTER(A.zh_zstd_frame), I64, P, I64, P, CH, SZ]),
     "zh_debug_zstd_decode_kernel_ms": (C.c_double, []),
@@ -554,6 +564,42 @@ class DeviceContext:
         check(self.L.zh_debug_zstd_xxh64(self.h, arr, n, out))
         return [int(out[i]) for i in range(n)]
 
+    def gzip_encode_batch_raw(self, sources, blocksize=0, stream=None, take=None):
+        """zh_gzip_encode_bound + zh_gzip_encode_batch over (device address, nbytes) pairs:
+        (the host buffer the members arrived in, [(dst_off, cbytes)] per source).  `take(n)`: a
+        uint8 array of n bytes to receive them (default: a fresh one)."""
+        import numpy as np
+        n = len(sources)
+        arr = (A.zh_gzip_enc_frame * max(1, n))()
+        for i, (addr, nb) in enumerate(sources):
+            arr[i].src, arr[i].nbytes = addr, int(nb)
+        prm = A.zh_gzip_enc_params(int(blocksize))
+        bound = self.L.zh_gzip_encode_bound(arr, n, C.byref(prm))
+        if bound < 0:
+            raise ZhError(int(-bound), "gzip encode: blocksize >= 0, sizes >= 0")
+        out = (take or (lambda k: np.empty(k, np.uint8)))(max(1, bound))
+        err = C.create_string_buffer(1024)
+        check(self.L.zh_gzip_encode_batch(self.h, arr, n, C.byref(prm), P(out.ctypes.data),
+                                          bound, P(stream), err, 1024), err)
+        return out, [(int(arr[i].dst_off), int(arr[i].cbytes)) for i in range(n)]
+
+    def gzip_encode_batch(self, sources, blocksize=0, stream=None, take=None):
+        """The gzip members of (device address, nbytes) sources as a list of bytes."""
+        out, rows = self.gzip_encode_batch_raw(sources, blocksize, stream, take)
+        mv = memoryview(out)
+        return [bytes(mv[o:o + n]) for o, n in rows]
+
+    def gzip_crc32(self, sources):
+        """zh_debug_gzip_crc32: CRC-32 of (device address, nbytes) buffers by the hash kernel of
+        the gzip batch."""
+        n = len(sources)
+        arr = (A.zh_gzip_enc_frame * max(1, n))()
+        for i, (addr, nb) in enumerate(sources):
+            arr[i].src, arr[i].nbytes = addr, int(nb)
+        out = (U32 * max(1, n))()
+        check(self.L.zh_debug_gzip_crc32(self.h, arr, n, out))
+        return [int(out[i]) for i in range(n)]
+
     def host_staging(self, nbytes):
         """zh_host_staging: the context's page-locked staging (valid until the next call)."""
         p = P()
@@ -750,6 +796,35 @@ def zstd_compress(data, checksum=True, blocksize=0):
     check(L.zh_zstd_compress(data, len(data), C.byref(prm), out, n.value, C.byref(n), err, 256),
           err)
     return bytes(out[:n.value])
+
+
+def gzip_compress(data, blocksize=0):
+    """zh_gzip_compress (no device): one gzip member of `data`, its content cut into blocks of
+    `blocksize` bytes (0: the default) that are compressed on their own."""
+    L = lib()
+    data = bytes(data)
+    prm = A.zh_gzip_enc_params(int(blocksize))
+    n = SZ()
+    err = C.create_string_buffer(256)
+    check(L.zh_gzip_compress(data, len(data), C.byref(prm), None, 0, C.byref(n), err, 256), err)
+    out = (C.c_char * n.value)()
+    check(L.zh_gzip_compress(data, len(data), C.byref(prm), out, n.value, C.byref(n), err, 256),
+          err)
+    return bytes(out[:n.value])
+
+
+def crc32(data, crc=0):
+    """zh_crc32 (no device): CRC-32 of `data` continuing from `crc`, as zlib.crc32."""
+    data = bytes(data)
+    return int(lib().zh_crc32(int(crc), data, len(data)))
+
+
+def gzip_encode_kernel_parts_ms():
+    """zh_debug_gzip_encode_kernel_parts_ms: {"match", "coder", "crc", "gather"} of the last
+    zh_gzip_encode_batch, in milliseconds."""
+    out = (C.c_double * 4)()
+    lib().zh_debug_gzip_encode_kernel_parts_ms(out)
+    return dict(zip(("match", "coder", "crc", "gather"), (float(v) for v in out)))
 
 
 def blosc_compress(data, typesize, shuffle, blocksize=0):

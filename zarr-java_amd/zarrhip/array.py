@@ -14,7 +14,8 @@ which one batched call decodes on the device when the codec is the chain's only 
 (ZH_BLOSC_DEVICE, zh_blosc_decode_batch; ZH_ZSTD_DEVICE, zh_zstd_decode_batch), and blosc LZ4 and
 zstd frames, which Array.write
 compresses on the device (ZH_BLOSC_ENCODE_DEVICE, zh_blosc_encode_batch; ZH_ZSTD_ENCODE_DEVICE,
-zh_zstd_encode_batch).
+zh_zstd_encode_batch), as it does gzip members when asked to (ZH_GZIP_ENCODE_DEVICE=1,
+zh_gzip_encode_batch).
 """
 import atexit
 import ctypes as C
@@ -28,7 +29,7 @@ import numpy as np
 
 from . import _abi as A
 from . import _lib
-from .codecs import BloscCodec, ZstdCodec, device_chain, host_bb_decode, host_bb_encode
+from .codecs import BloscCodec, GzipCodec, ZstdCodec, device_chain, host_bb_decode, host_bb_encode
 from .errors import UnsupportedChainError, ZarrException, raise_for
 from .metadata import ZARR_JSON, ArrayMetadata
 
@@ -56,6 +57,11 @@ BLOSC_ENCODE_DEVICE_DEFAULT = "1"
 # ZH_ZSTD_ENCODE_DEVICE: the same for a zstd chain (zh_zstd_encode_batch), and "1" for the same
 # reason (DESIGN.md "Zstd frames encoded on the device").
 ZSTD_ENCODE_DEVICE_DEFAULT = "1"
+# ZH_GZIP_ENCODE_DEVICE: "1" sends a gzip chain's members to the device (zh_gzip_encode_batch).
+# The default is "0": the device writer has no dynamic-Huffman blocks, so bytes that LZ alone does
+# not shrink are stored where zlib would still compress them (DESIGN.md "Gzip members encoded on
+# the device"); with the switch unset every stored byte is zlib's.
+GZIP_ENCODE_DEVICE_DEFAULT = "0"
 
 
 class _Deferred:
@@ -810,6 +816,7 @@ class Array:
                 raise_for(e)
             self.last_write_info = {"blosc_device_frames": 0, "blosc_host_frames": 0,
                                     "zstd_device_frames": 0, "zstd_host_frames": 0,
+                                    "gzip_device_frames": 0, "gzip_host_frames": 0,
                                     "raw_bytes": sum(sizes), "stored_bytes": sum(sizes)}
             return
         L = _lib.lib()
@@ -817,7 +824,8 @@ class Array:
         src = dev.malloc(max(1, data.nbytes))
         bufs = []
         info = {"blosc_device_frames": 0, "blosc_host_frames": 0, "zstd_device_frames": 0,
-                "zstd_host_frames": 0, "raw_bytes": 0, "stored_bytes": 0}
+                "zstd_host_frames": 0, "gzip_device_frames": 0, "gzip_host_frames": 0,
+                "raw_bytes": 0, "stored_bytes": 0}
         try:
             dev.memcpy(src, data.ctypes.data, data.nbytes, 0)
             bufs = [dev.malloc(cap) for _ in coords]
@@ -877,6 +885,8 @@ class Array:
             return bb[0].encode(enc, self.metadata.data_type.getByteCount())
         if info is not None and self._zstd_chain():
             info["zstd_host_frames"] += 1
+        if info is not None and self._gzip_chain():
+            info["gzip_host_frames"] += 1
         return host_bb_encode(bb, enc)
 
     def _zstd_chain(self):
@@ -884,12 +894,19 @@ class Array:
         bb = self.chain.inner_host_bb if self.chain.chain["sharded"] else self.chain.host_bb
         return len(bb) == 1 and isinstance(bb[0], ZstdCodec)
 
+    def _gzip_chain(self):
+        """The chain's host byte-to-byte stages are exactly one GzipCodec."""
+        bb = self.chain.inner_host_bb if self.chain.chain["sharded"] else self.chain.host_bb
+        return len(bb) == 1 and isinstance(bb[0], GzipCodec)
+
     def _encode_device(self):
-        """"blosc" / "zstd" when Array.write makes the chain's frames on the device
-        (zh_blosc_encode_batch / zh_zstd_encode_batch), else None: the codec is the only host
-        byte-to-byte stage, one device is in use and the codec's switch (ZH_BLOSC_ENCODE_DEVICE /
-        ZH_ZSTD_ENCODE_DEVICE) is not "0".  Blosc: its cname is lz4 / lz4hc (the one blosc
-        compressor written here; clevel is not honoured, as zstd's level is not)."""
+        """"blosc" / "zstd" / "gzip" when Array.write makes the chain's frames on the device
+        (zh_blosc_encode_batch / zh_zstd_encode_batch / zh_gzip_encode_batch), else None: the
+        codec is the only host byte-to-byte stage, one device is in use and the codec's switch
+        (ZH_BLOSC_ENCODE_DEVICE / ZH_ZSTD_ENCODE_DEVICE) is not "0", or, for gzip, whose host
+        route is zlib and stores other bytes, ZH_GZIP_ENCODE_DEVICE is "1".  Blosc: its cname is
+        lz4 / lz4hc (the one blosc compressor written here; clevel is not honoured, as the level
+        of zstd and gzip is not)."""
         if len(devices()) != 1:
             return None
         bb = self.chain.inner_host_bb if self.chain.chain["sharded"] else self.chain.host_bb
@@ -899,10 +916,13 @@ class Array:
         if self._zstd_chain():
             on = os.environ.get("ZH_ZSTD_ENCODE_DEVICE", ZSTD_ENCODE_DEVICE_DEFAULT) != "0"
             return "zstd" if on else None
+        if self._gzip_chain():
+            on = os.environ.get("ZH_GZIP_ENCODE_DEVICE", GZIP_ENCODE_DEVICE_DEFAULT) == "1"
+            return "gzip" if on else None
         return None
 
     def _frames_device(self, dev, bufs, sizes, info, kind):
-        """The stored objects of the chunks with sz > 0, their blosc or zstd frames (`kind`)
+        """The stored objects of the chunks with sz > 0, their frames (`kind`: blosc, zstd, gzip)
         compressed on the device in one batch over the chunk buffers: {chunk number: bytes}.
         Unsharded: the chunk is one frame.  Sharded: only the stored index comes back as it is;
         every present entry is one frame, and the shard is put together as _wrap_inner does."""
@@ -914,9 +934,12 @@ class Array:
 
             def batch(sources, take):
                 return dev.blosc_encode_batch(sources, ts, shuffle, blocksize, take=take)
-        else:
+        elif kind == "zstd":
             def batch(sources, take):
                 return dev.zstd_encode_batch(sources, bool(codec.checksum), take=take)
+        else:
+            def batch(sources, take):
+                return dev.gzip_encode_batch(sources, take=take)
         sources, shards = [], {}
         if sharded:
             n_in = self._n_inner()

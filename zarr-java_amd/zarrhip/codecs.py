@@ -234,7 +234,10 @@ class Crc32cCodec(Codec):
 
 
 class GzipCodec(Codec):
-    """GzipCodec (M/v3/codec/core/GzipCodec.java:35-46) — host only."""
+    """GzipCodec (M/v3/codec/core/GzipCodec.java:35-46) — host only: zlib both ways.
+    Array.write makes a gzip chain's members on the device instead when ZH_GZIP_ENCODE_DEVICE
+    is 1 (zh_gzip_encode_batch: other bytes than zlib's, `level` not honoured); decode reads
+    both."""
     name, kind = "gzip", "bb"
 
     def __init__(self, level=5):
