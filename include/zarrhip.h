@@ -850,6 +850,72 @@ double zh_debug_zstd_decode_kernel_ms(void);
 int64_t zh_debug_zstd_blocks(const void* src, size_t srclen, int64_t* rows, int64_t cap,
                              char* err, size_t errlen);
 
+/* ---- gzip members decoded on the host or on the device, a batch at a time ----------------
+ * The read side of zh_gzip_encode_batch, in the shape of the zstd batch above.  The decoder
+ * (csrc/zh_gzip_dec.h, RFC 1951 / RFC 1952) reads the FIRST member of a buffer and ignores what
+ * follows it, as zlib.decompress(b, 31) does: stored, fixed and dynamic blocks; FEXTRA, FNAME,
+ * FCOMMENT and FHCRC headers; it accepts and rejects what zlib's inflate accepts and rejects.
+ *
+ * zh_gzip_decompress: host, no device.  dst == NULL: the size query, a decoding pass that stores
+ * nothing (never ISIZE alone).  Otherwise dstcap must hold the content; the CRC-32 and ISIZE are
+ * verified.  Errors are ZH_EDATA with zlib's wording behind "gzip: " (e.g. "gzip: invalid
+ * distance too far back", "gzip: incorrect data check"); content larger than dstcap is
+ * ZH_EINVAL. */
+int zh_gzip_decompress(const void* src, size_t srclen, void* dst, size_t dstcap, size_t* dstlen,
+                       char* err, size_t errlen);
+
+typedef struct zh_gzip_frame {
+  const void* src;   /* the stored member, host memory                              */
+  int64_t srclen;
+  int64_t dst_off;   /* out (plan): offset in the batch destination, 256-B aligned  */
+  int64_t nbytes;    /* out (plan): decoded size                                    */
+  int32_t where;     /* out (plan): 0 device, 1 host (zh_gzip_decompress, then H2D).
+                        zh_gzip_decode_batch also sets 1 on a member its kernel refused
+                        and zh_gzip_decompress then accepted                        */
+  int32_t status;    /* out: ZH_OK or this frame's error                            */
+  int32_t host_only; /* in: non-zero plans the frame for the host                   */
+} zh_gzip_frame;
+
+/* No device needed: walks the gzip header of every frame, no block.  A header error is reported
+ * for the first bad frame in batch order with zh_gzip_decompress's status and text (that frame's
+ * status field is set).  where = 0 takes nbytes from the frame's last four bytes and requires
+ * host_only == 0, at least 2 + 8 bytes behind the header and nbytes <= 1032 x (srclen - header
+ * - 8), DEFLATE's largest expansion; every other frame is where = 1 with nbytes from the size
+ * query (whose failure is reported the same way).  Returns the destination bytes or
+ * -zh_status. */
+int64_t zh_gzip_batch_plan(zh_gzip_frame* frames, int64_t n, char* err, size_t errlen);
+
+/* Plans as above, stages the compressed bytes H2D through the context's pinned ring, decodes on
+ * `stream` (NULL: the context's) one wavefront per member, in slabs of at most 128 MiB of decoded
+ * bytes (a larger member is its own slab), hashes the decoded members with the CRC-32 kernel of
+ * zh_gzip_encode_batch, compares with the stored CRC-32 on the host, and waits.  A member the
+ * kernel flagged (it also requires the planned nbytes and that the member ends with the frame),
+ * or whose CRC-32 differs, goes through zh_gzip_decompress in batch order: a failure is the
+ * call's status and text; a success that fits the frame's slot (nbytes rounded up to 256) is
+ * copied up, nbytes is corrected and where becomes 1; a success larger than its slot (trailing
+ * bytes, or a member over 4 GiB, hid the real ISIZE) sets that frame's status to
+ * ZH_EUNSUPPORTED and, unless an error comes first, the call returns ZH_EUNSUPPORTED with
+ * "gzip: decoded size exceeds the planned size": plan such frames again with host_only set.
+ * dst is device memory of dstcap >= the plan's bytes.  After a failed call dst is undefined;
+ * the context stays usable. */
+int zh_gzip_decode_batch(zh_ctx* ctx, zh_gzip_frame* frames, int64_t n, void* dst,
+                         int64_t dstcap, void* stream, char* err, size_t errlen);
+
+/* Diagnostic: milliseconds the decode and CRC-32 kernels of the last successful
+ * zh_gzip_decode_batch in this process took, by device events, summed over its slabs (-1: none
+ * yet). */
+double zh_debug_gzip_decode_kernel_ms(void);
+
+/* Diagnostic, no device: the DEFLATE blocks of the first member as rows of 9 int64: block type
+ * (0 stored, 1 fixed, 2 dynamic), stored bits (header bits included), decoded bytes, the number
+ * of literal/length and of distance codes (HLIT + 257 and HDIST + 1; 288 and 32 for a fixed
+ * block, -1 for a stored one), the largest literal/length code length, the largest distance
+ * code length, the number of distance codes in use, and the largest match distance of the
+ * block (0: no match).  Writes up to `cap` rows to `rows` (may be NULL) and returns their
+ * number, or -zh_status for a member the decoder rejects. */
+int64_t zh_debug_gzip_blocks(const void* src, size_t srclen, int64_t* rows, int64_t cap,
+                             char* err, size_t errlen);
+
 /* dst block b ← src block src_block[b] (device buffers, blocks of block_bytes, a multiple of
  * 16; 16-byte aligned; src_block on the host), synchronous: re-lays out encoded shards, e.g.
  * the bench's shuffled inner-chunk order. */

@@ -272,6 +272,12 @@ int pipe_out_ring(zh_ctx* ctx, int* lanes, int64_t* window);
 // zh_zstd_enc_kernels.hip: XXH64 (seed 0) of n device buffers, one wave each, on stream s;
 // d_jobs: n x {uint64 address, uint64 nbytes} and d_hashes[n], both in device memory.
 int zstd_hash_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint64_t* d_hashes);
+// zh_gzip_enc_kernels.hip: the raw CRC-32 registers (zh_gz::crc_raw from 0) of n device spans on
+// stream s; d_jobs: n x {uint64 address, uint32 nbytes <= 64 KiB, uint32 0} and d_raw[n], both in
+// device memory.  The caller folds the spans of a buffer (zh_gz::crc_append, crc_finish).
+int gzip_crc_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint32_t* d_raw);
+// zh_gzip.cpp: the plan of zh_gzip_batch_plan; *total: the destination bytes.
+int gzip_plan(zh_gzip_frame* frames, int64_t n, int64_t* total, char* err, size_t errlen);
 // One region over several contexts (zh_array_read_multi_routed / zh_array_read_pieces_multi).
 int read_multi_impl(zh_ctx* const* ctxs, int ndev, int root, const zh_array_meta* meta,
                     const SrcDesc* chunks, int64_t nchunks, const int64_t* offset,

@@ -547,6 +547,14 @@ int64_t bound_of(const zh_gzip_enc_frame* frames, int64_t n, const zh_gzip_enc_p
 
 }  // namespace
 
+int zh::gzip_crc_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint32_t* d_raw) {
+  static_assert(sizeof(::CrcJob) == 16, "the layout zh_ctx.h describes");
+  if (n == 0) return ZH_OK;
+  hipLaunchKernelGGL(gzip_crc32_kernel, dim3(n), dim3(kThreads), 0, s, (const ::CrcJob*)d_jobs,
+                     zh_gz::xpow8(kPiece), d_raw);
+  return hipGetLastError() == hipSuccess ? ZH_OK : ZH_EHIP;
+}
+
 extern "C" {
 
 int64_t zh_gzip_encode_bound(const zh_gzip_enc_frame* frames, int64_t n,

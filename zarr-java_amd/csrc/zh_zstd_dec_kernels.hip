@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "zh_ctx.h"
+#include "zh_dec_lanes.h"
 #include "zh_stager.h"
 #include "zh_zstd_dec.h"
 
@@ -66,34 +67,7 @@ struct HashJob {  // zstd_xxh64_kernel's
   uint64_t src, n;
 };
 
-// The lane policy of zh_zstd_dec.h for one wave.
-struct ZdLanes {
-  static constexpr uint32_t W = 64;
-  uint32_t l;
-  __device__ uint32_t lane() const { return l; }
-  __device__ bool first() const { return l == 0; }
-  __device__ static void order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
-  __device__ bool all(bool v) { return __all(v ? 1 : 0) != 0; }
-  __device__ void copy(uint8_t* d, const uint8_t* s, uint64_t n) {
-    for (uint64_t k = l; k < n; k += 64) d[k] = s[k];
-  }
-  __device__ void fill(uint8_t* d, uint32_t v, uint64_t n) {
-    for (uint64_t k = l; k < n; k += 64) d[k] = (uint8_t)v;
-  }
-  __device__ void match(uint8_t* d, uint64_t o, uint64_t off, uint64_t n) {
-    order();
-    const uint8_t* b = d + o - off;
-    if (off >= n) {
-      for (uint64_t k = l; k < n; k += 64) d[o + k] = b[k];
-    } else {  // pattern replication: only bytes below o are read
-      for (uint64_t k = l; k < n; k += 64) d[o + k] = b[k % off];
-    }
-  }
-};
+// The lane policy of zh_zstd_dec.h for one wave: ZdLanes (zh_dec_lanes.h).
 
 __global__ __launch_bounds__(kThreads) void zstd_decode_kernel(
     const uint8_t* __restrict__ src, uint8_t* dst, uint8_t* lit,

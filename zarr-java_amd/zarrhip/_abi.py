@@ -131,6 +131,13 @@ class zh_gzip_enc_frame(C.Structure):
                 ("cbytes", C.c_int64), ("status", C.c_int32)]
 
 
+class zh_gzip_frame(C.Structure):
+    """One gzip member of a batched device decode (zarrhip.h zh_gzip_frame)."""
+    _fields_ = [("src", C.c_void_p), ("srclen", C.c_int64), ("dst_off", C.c_int64),
+                ("nbytes", C.c_int64), ("where", C.c_int32), ("status", C.c_int32),
+                ("host_only", C.c_int32)]
+
+
 class zh_file_store(C.Structure):
     """A FilesystemStore as the file reads name it (zarrhip.h zh_file_store)."""
     _fields_ = [("root", C.c_char_p), ("name", C.c_char_p)]

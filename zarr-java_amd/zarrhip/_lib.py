@@ -129,6 +129,11 @@ _SIGS = {
     "zh_zstd_decode_batch": (C.c_int, [P, C.POINTER(A.zh_zstd_frame), I64, P, I64, P, CH, SZ]),
     "zh_debug_zstd_decode_kernel_ms": (C.c_double, []),
     "zh_debug_zstd_blocks": (I64, [P, SZ, PI64, I64, CH, SZ]),
+    "zh_gzip_decompress": (C.c_int, [P, SZ, P, SZ, C.POINTER(SZ), C.c_char_p, SZ]),
+    "zh_gzip_batch_plan": (I64, [C.POINTER(A.zh_gzip_frame), I64, CH, SZ]),
+    "zh_gzip_decode_batch": (C.c_int, [P, C.POINTER(A.zh_gzip_frame), I64, P, I64, P, CH, SZ]),
+    "zh_debug_gzip_decode_kernel_ms": (C.c_double, []),
+    "zh_debug_gzip_blocks": (I64, [P, SZ, PI64, I64, CH, SZ]),
     "zh_device_malloc": (C.c_int, [P, SZ, C.POINTER(P)]),
     "zh_device_malloc_ex": (C.c_int, [P, SZ, C.c_uint, C.POINTER(P)]),
     "zh_device_free": (C.c_int, [P, P]),
@@ -499,6 +504,40 @@ class DeviceContext:
         del keep
         return ptr, [(arr[i].dst_off, arr[i].nbytes, arr[i].where) for i in range(len(frames))]
 
+    def gzip_decode_batch(self, frames, stream=None):
+        """zh_gzip_batch_plan + zh_gzip_decode_batch over gzip members (bytes-like, or (address,
+        nbytes) pairs of host memory the caller keeps alive; a third element of a tuple, or
+        `host_only` in a (bytes, host_only) pair, plans the frame for the host): returns the
+        device buffer holding every decoded member and, per frame, (dst_off, nbytes, where).
+        The caller frees the buffer (self.free).  A member whose size the plan could not read
+        off its last four bytes ("exceeds the planned size") is planned for the host and the
+        batch decoded once more; a second such failure is raised."""
+        arr, keep = gzip_frame_array(frames)
+        n = len(frames)
+        for attempt in (0, 1):
+            err = C.create_string_buffer(1024)
+            total = self.L.zh_gzip_batch_plan(arr, n, err, 1024)
+            if total < 0:
+                # after the errors of the frames before the one the plan refuses
+                k = next(i for i in range(n) if arr[i].status != A.ZH_OK)
+                bad = ZhError(int(-total), err.value.decode())
+                if k > 0:
+                    self.free(self.gzip_decode_batch(frames[:k], stream)[0])
+                raise bad
+            ptr = self.malloc(max(256, total), A.ZH_MALLOC_PLAIN)
+            st = self.L.zh_gzip_decode_batch(self.h, arr, n, P(ptr), max(256, total), P(stream),
+                                             err, 1024)
+            if st == A.ZH_OK:
+                del keep
+                return ptr, [(arr[i].dst_off, arr[i].nbytes, arr[i].where) for i in range(n)]
+            self.free(ptr)
+            over = [i for i in range(n) if arr[i].status == A.ZH_EUNSUPPORTED]
+            if (attempt == 1 or st != A.ZH_EUNSUPPORTED or not over or
+                    b"exceeds the planned size" not in err.value):
+                check(st, err)
+            for i in over:
+                arr[i].host_only = 1
+
     def blosc_encode_batch_raw(self, sources, typesize, shuffle, blocksize=0, stream=None,
                                take=None):
         """zh_blosc_encode_bound + zh_blosc_encode_batch over (device address, nbytes) pairs:
@@ -811,6 +850,69 @@ def gzip_compress(data, blocksize=0):
     check(L.zh_gzip_compress(data, len(data), C.byref(prm), out, n.value, C.byref(n), err, 256),
           err)
     return bytes(out[:n.value])
+
+
+def gzip_frame_array(frames):
+    """zh_gzip_frame[] for bytes-like members, (address, nbytes) pairs or (address, nbytes,
+    host_only) triples; returns (array, keepalive)."""
+    arr, keep = frame_array([f[:2] if isinstance(f, tuple) else f for f in frames],
+                            A.zh_gzip_frame)
+    for i, f in enumerate(frames):
+        if isinstance(f, tuple) and len(f) > 2:
+            arr[i].host_only = 1 if f[2] else 0
+    return arr, keep
+
+
+def gzip_decompress(member):
+    """zh_gzip_decompress (no device): the content of the first gzip member of `member`, sized
+    by the size query."""
+    L = lib()
+    member = bytes(member)
+    src = member or b"\0"
+    n = SZ()
+    err = C.create_string_buffer(256)
+    check(L.zh_gzip_decompress(src, len(member), None, 0, C.byref(n), err, 256), err)
+    out = (C.c_char * max(1, n.value))()
+    check(L.zh_gzip_decompress(src, len(member), out, n.value, C.byref(n), err, 256), err)
+    return bytes(out[:n.value])
+
+
+def gzip_size(member):
+    """zh_gzip_decompress's size query (no device)."""
+    member = bytes(member)
+    n = SZ()
+    err = C.create_string_buffer(256)
+    check(lib().zh_gzip_decompress(member or b"\0", len(member), None, 0, C.byref(n), err, 256),
+          err)
+    return int(n.value)
+
+
+def gzip_batch_plan(frames):
+    """zh_gzip_batch_plan (no device): (destination bytes, [(dst_off, nbytes, where)]); frames as
+    gzip_frame_array takes them."""
+    arr, keep = gzip_frame_array(frames)
+    err = C.create_string_buffer(1024)
+    total = lib().zh_gzip_batch_plan(arr, len(frames), err, 1024)
+    if total < 0:
+        check(int(-total), err)
+    return int(total), [(arr[i].dst_off, arr[i].nbytes, arr[i].where)
+                        for i in range(len(frames))]
+
+
+def gzip_blocks(member):
+    """zh_debug_gzip_blocks (no device): the DEFLATE blocks of the first member, 9 ints each:
+    type, stored bits, decoded bytes, literal/length codes, distance codes, largest
+    literal/length code length, largest distance code length, distance codes in use, largest
+    match distance."""
+    L = lib()
+    b = (C.c_char * max(1, len(member))).from_buffer_copy(bytes(member) or b"\0")
+    err = C.create_string_buffer(1024)
+    n = L.zh_debug_gzip_blocks(b, len(member), None, 0, err, 1024)
+    if n < 0:
+        check(int(-n), err)
+    rows = (C.c_int64 * max(1, 9 * n))()
+    L.zh_debug_gzip_blocks(b, len(member), rows, n, err, 1024)
+    return [tuple(rows[9 * k:9 * k + 9]) for k in range(n)]
 
 
 def crc32(data, crc=0):

@@ -9,10 +9,10 @@ chunk codec work done by the HIP path through the C-ABI (libzarrhip.so).
   access()                   M/core/Array.java:483-536   (ArrayAccessor)
 
 Byte-to-byte compressors stay on the host (north star): their frames are decoded here and
-the raw chunk bytes are handed to the device — except blosc and zstd frames,
-which one batched call decodes on the device when the codec is the chain's only host stage
-(ZH_BLOSC_DEVICE, zh_blosc_decode_batch; ZH_ZSTD_DEVICE, zh_zstd_decode_batch), and blosc LZ4 and
-zstd frames, which Array.write
+the raw chunk bytes are handed to the device — except blosc and zstd frames
+and gzip members, which one batched call decodes on the device when the codec is the chain's only
+host stage (ZH_BLOSC_DEVICE, zh_blosc_decode_batch; ZH_ZSTD_DEVICE, zh_zstd_decode_batch;
+ZH_GZIP_DEVICE, zh_gzip_decode_batch), and blosc LZ4 and zstd frames, which Array.write
 compresses on the device (ZH_BLOSC_ENCODE_DEVICE, zh_blosc_encode_batch; ZH_ZSTD_ENCODE_DEVICE,
 zh_zstd_encode_batch), as it does gzip members when asked to (ZH_GZIP_ENCODE_DEVICE=1,
 zh_gzip_encode_batch).
@@ -49,6 +49,15 @@ BLOSC_DEVICE_DEFAULT = "1"
 # ZSTD_DEVICE_MIN_FRAMES is None, and the device route is behind ZH_ZSTD_DEVICE=2.
 ZSTD_DEVICE_DEFAULT = "1"
 ZSTD_DEVICE_MIN_FRAMES = None
+# ZH_GZIP_DEVICE: the same for chains whose only host byte-to-byte stage is one v3 GzipCodec
+# (zh_gzip_decode_batch), with the same three values.  "1" (the default) follows the rule of
+# DESIGN.md ("Gzip members on the device"): a read goes to the device when it holds at least
+# GZIP_DEVICE_MIN_FRAMES members.  In the record (profiles/gzip_decode/lab.json) few large members
+# lose outright and many small members have the lower median but not by more than the spread, so
+# the default sends nothing to the device: GZIP_DEVICE_MIN_FRAMES is None, and the device route is
+# behind ZH_GZIP_DEVICE=2.
+GZIP_DEVICE_DEFAULT = "1"
+GZIP_DEVICE_MIN_FRAMES = None
 # ZH_BLOSC_ENCODE_DEVICE: Array.write compresses a blosc LZ4 chain's frames on the device in one
 # batch (zh_blosc_encode_batch) instead of copying every raw chunk back and compressing it here.
 # It stays "1" whatever the write times say: the stored size is what the codec was asked for,
@@ -87,6 +96,14 @@ def _raise_zstd(err):
         raise UnsupportedChainError(str(err)) from None
     if err.status in (A.ZH_EDATA, A.ZH_EINVAL):
         raise ZarrException(f"Error in decoding zstd: {err}") from None
+    raise_for(err)
+
+
+def _raise_gzip(err):
+    """A _lib.ZhError of the batched gzip decode as the reference's GzipCodec.decode raises it
+    (M/v3/codec/core/GzipCodec.java:42-43)."""
+    if err.status in (A.ZH_EDATA, A.ZH_EINVAL):
+        raise ZarrException("Error in decoding gzip.") from None
     raise_for(err)
 
 
@@ -545,6 +562,10 @@ class Array:
             self._read_frames_device(coords, offset, shape, out_addr, flags, devs[0], parallel,
                                      t_enter, t0, devs[0].zstd_decode_batch, _raise_zstd, "zstd")
             return
+        if self._gzip_device(devs, coords):
+            self._read_frames_device(coords, offset, shape, out_addr, flags, devs[0], parallel,
+                                     t_enter, t0, devs[0].gzip_decode_batch, _raise_gzip, "gzip")
+            return
         lease = []  # staging buffers of this read, back to the pool after the device read
         sharded = self.chain.chain["sharded"]
         try:
@@ -566,6 +587,7 @@ class Array:
                 0 if s is None else len(s[1].pieces) if s[0] == "pieces" else 1 for s in sources)
             n_blosc = n_frames if self._blosc_chain() else 0
             n_zstd = n_frames if self._zstd_chain() else 0
+            n_gzip = n_frames if self._gzip_chain() else 0
             keep = []
             try:
                 if sharded:  # index + pieces (or whole objects as one piece at 0)
@@ -612,7 +634,8 @@ class Array:
         self.last_read_timing = {"prep_s": t0 - t_enter, "stage_s": t1 - t0,
                                  "device_s": time.perf_counter() - t1,
                                  "blosc_device_frames": 0, "blosc_host_frames": n_blosc,
-                                 "zstd_device_frames": 0, "zstd_host_frames": n_zstd}
+                                 "zstd_device_frames": 0, "zstd_host_frames": n_zstd,
+                                 "gzip_device_frames": 0, "gzip_host_frames": n_gzip}
 
     def _blosc_chain(self):
         """The chain's host byte-to-byte stages are exactly one BloscCodec (v3 or v2)."""
@@ -643,11 +666,27 @@ class Array:
         per = self._n_inner() if self.chain.chain["sharded"] else 1
         return len(coords) * per >= ZSTD_DEVICE_MIN_FRAMES
 
+    def _gzip_device(self, devs, coords=()):
+        """One device, a gzip chain and ZH_GZIP_DEVICE: "0" never, "2" always, "1" when the read
+        has at least GZIP_DEVICE_MIN_FRAMES members (a shard counts its inner chunks)."""
+        if len(devs) != 1 or not self._gzip_chain():
+            return False
+        mode = os.environ.get("ZH_GZIP_DEVICE", GZIP_DEVICE_DEFAULT)
+        if mode == "0":
+            return False
+        if mode == "2":
+            return True
+        if GZIP_DEVICE_MIN_FRAMES is None:
+            return False
+        per = self._n_inner() if self.chain.chain["sharded"] else 1
+        return len(coords) * per >= GZIP_DEVICE_MIN_FRAMES
+
     def _read_frames_device(self, coords, offset, shape, out_addr, flags, dev, parallel, t_enter,
                             t0, decode_batch, raise_frame, codec):
-        """_read_into for a chain whose only host stage is blosc or zstd, on one device: the
+        """_read_into for a chain whose only host stage is blosc, zstd or gzip, on one device: the
         store reads of every chunk (a shard: its index check and per-entry range reads), one
-        batched decode (`decode_batch`: DeviceContext.blosc_decode_batch / zstd_decode_batch) over
+        batched decode (`decode_batch`: DeviceContext.blosc_decode_batch / zstd_decode_batch /
+        gzip_decode_batch) over
         all frames of the read, then the device read over sources in the batch buffer.
         `raise_frame` raises a frame's _lib.ZhError as the codec's host decode does; `codec`
         names the counters of last_read_timing."""
@@ -740,6 +779,7 @@ class Array:
             "prep_s": t0 - t_enter, "stage_s": t1 - t0, "device_s": time.perf_counter() - t1,
             "blosc_device_frames": 0, "blosc_host_frames": 0,
             "zstd_device_frames": 0, "zstd_host_frames": 0,
+            "gzip_device_frames": 0, "gzip_host_frames": 0,
             codec + "_device_frames": sum(1 for r in rows if r[2] != 1),
             codec + "_host_frames": sum(1 for r in rows if r[2] == 1)}
 

@@ -8,7 +8,10 @@
 The objects are host-side descriptions; `device_chain` maps a codec list onto the
 zh_codec_chain the HIP path executes (bytes/transpose/sharding/crc32c-index).  Byte-to-
 byte compressors (gzip, blosc, zstd, inner crc32c) stay on the host (north star): they
-are applied by `host_bb_decode` before the bytes reach the device.
+are applied by `host_bb_decode` before the bytes reach the device.  Array.read can hand the
+frames of a chain whose only such stage is blosc, zstd or gzip to the device in one batch instead
+(ZH_BLOSC_DEVICE, ZH_ZSTD_DEVICE, ZH_GZIP_DEVICE; array.py): the codec objects here are not
+involved then.
 """
 import gzip as _gzip
 import struct
@@ -237,7 +240,10 @@ class GzipCodec(Codec):
     """GzipCodec (M/v3/codec/core/GzipCodec.java:35-46) — host only: zlib both ways.
     Array.write makes a gzip chain's members on the device instead when ZH_GZIP_ENCODE_DEVICE
     is 1 (zh_gzip_encode_batch: other bytes than zlib's, `level` not honoured); decode reads
-    both."""
+    both.  Array.read decodes a gzip chain's members on the device instead when ZH_GZIP_DEVICE
+    says so (zh_gzip_decode_batch, the library's own DEFLATE reader; a corrupt member is then
+    ZarrException("Error in decoding gzip."), the reference's).  decode() here stays zlib and a
+    corrupt member raises the bare zlib.error: moving it to zh_gzip_decompress is a follow-up."""
     name, kind = "gzip", "bb"
 
     def __init__(self, level=5):
