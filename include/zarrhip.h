@@ -748,13 +748,18 @@ int zh_debug_zstd_xxh64(zh_ctx* ctx, const zh_zstd_enc_frame* frames, int64_t n,
  * `blocksize` bytes, each compressed on its own (greedy LZ over a 1024-slot table, no match
  * reaching before the block) into one byte-aligned segment: a fixed-Huffman DEFLATE block
  * followed by an empty stored block, or, when that is not smaller, a stored block (5 bytes over
- * raw).  The member ends with the final empty fixed block 03 00, the CRC-32 and the size.  No
- * dynamic-Huffman blocks: bytes that LZ alone does not shrink are stored.  No member is larger
- * than 20 + n + 5 * ceil(n / blocksize): the bound.  The bytes are a pure function of (input,
- * block size): the host call and the batch call give the same member.  The codec's `level` is
- * not honoured. */
+ * raw).  The member ends with the final empty fixed block 03 00, the CRC-32 and the size.  With
+ * `dynamic` 0 there are no dynamic-Huffman blocks: bytes that LZ alone does not shrink are
+ * stored.  With `dynamic` 1 a dynamic-Huffman block (its own length-limited Huffman codes over
+ * the block's literals, lengths and distances, followed by the same empty stored block) is the
+ * block's segment when it is strictly smaller than both other forms.  No member is larger
+ * than 20 + n + 5 * ceil(n / blocksize): the bound, with either value.  The bytes are a pure
+ * function of (input, block size, dynamic): the host call and the batch call give the same
+ * member.  The codec's `level` is not honoured.  Callers zero the struct before they set a
+ * field: a field added later then keeps the behaviour of before. */
 typedef struct zh_gzip_enc_params {
   int32_t blocksize;  /* 0: default (16 KiB); below 1 KiB: 1 KiB; above 32 KiB: 32 KiB  */
+  int32_t dynamic;    /* 0: stored and fixed segments; 1: dynamic ones too; else ZH_EINVAL */
 } zh_gzip_enc_params;
 
 typedef struct zh_gzip_enc_frame {
@@ -791,11 +796,16 @@ int zh_gzip_encode_batch(zh_ctx* ctx, zh_gzip_enc_frame* frames, int64_t n,
 
 /* Diagnostics: milliseconds the kernels of the last successful zh_gzip_encode_batch took, by
  * device events, summed over its slabs (-1: none yet), and the same per kernel into out[4]:
- * match, coder, CRC-32, gather; CRC-32 of n device buffers by the batch's hash kernel and the
- * host combination into out[n] (host). */
+ * match, coder (with `dynamic` 1: histogram, code construction and coding), CRC-32, gather;
+ * CRC-32 of n device buffers by the batch's hash kernel and the host combination into out[n]
+ * (host); the code lengths the dynamic form gives `rows` histograms of `nsym` counts each
+ * (nsym <= 286, counts <= 2^22, limit 1..15) into lens[rows * nsym]: on the host when ctx is
+ * NULL, else one wavefront per row on the device (counts and lens are host memory). */
 double zh_debug_gzip_encode_kernel_ms(void);
 void zh_debug_gzip_encode_kernel_parts_ms(double out[4]);
 int zh_debug_gzip_crc32(zh_ctx* ctx, const zh_gzip_enc_frame* frames, int64_t n, uint32_t* out);
+int zh_debug_gzip_code_lengths(zh_ctx* ctx, const uint32_t* counts, int32_t nsym, int32_t limit,
+                               int64_t rows, uint8_t* lens);
 
 /* ---- zstd frames decoded on the device, a batch at a time -----------------------------
  * The read side of the batch above, in the shape of zh_blosc_decode_batch.  A stored chunk that

@@ -7,13 +7,17 @@
 // Segments: the content is cut into blocks of B bytes (the last one shorter); each is compressed
 // on its own with the `wide` matcher of zh_lz_match.h: no match reaches before the block's first
 // byte, so one wave can take one block, and B <= 32 KiB, DEFLATE's window, bounds every distance.
-// A block becomes one byte-aligned segment, the smaller of two forms (stored on a tie):
+// A block becomes one byte-aligned segment, the smallest of two forms, or of three when the
+// caller asks for it (zh_gzip_enc_params::dynamic = 1); stored wins a tie, fixed one against
+// dynamic:
 //   * fixed: header bits BFINAL 0, BTYPE 01; the fixed Huffman codes of RFC 1951 §3.2.6 (codes
 //     MSB first, extra bits LSB first, in an LSB-first bit stream); the end-of-block code; an
 //     empty stored block as a sync marker: bits 000, zero bits up to the byte boundary,
 //     00 00 ff ff;
-//   * stored: 00, LEN, NLEN, the block's bytes: 5 bytes over raw.
-// A third form (dynamic Huffman) would join the same choice without changing the layout.
+//   * stored: 00, LEN, NLEN, the block's bytes: 5 bytes over raw;
+//   * dynamic: header bits BFINAL 0, BTYPE 10; the block's own length-limited Huffman codes
+//     (code_lengths, plan_dynamic below), the symbols, the end-of-block code and the same sync
+//     marker.  It is chosen only when strictly smaller than both other forms.
 // So no member is larger than 20 + n + 5 * ceil(n / B), the bound the interface reports.
 // Two phases per block, as in the zstd writer:
 //   match_block    over a lane policy W: (literal length, match length, offset) records,
@@ -29,7 +33,10 @@
 //                  is stored exactly when the fixed form would pass n + 4 bytes, in both.
 // The CRC-32 is linear, so a content is hashed in spans that are combined with x^(8 len) mod P
 // (mulmod, xpow8, crc_finish): the device hashes spans in parallel, the host folds them.
-// The output is a pure function of (input bytes, B).
+//   deflate_block_dynamic  the same walk with the dynamic form in the choice: the block's
+//                  histogram first, then the exact sizes, then one table walk for either form.
+// The output is a pure function of (input bytes, B, dynamic).  Callers zero zh_gzip_enc_params
+// before they set a field: dynamic = 0 gives the two forms of before, byte for byte.
 #pragma once
 
 #include <stddef.h>
@@ -164,19 +171,31 @@ ZH_BS_HD uint32_t lit_bits(uint32_t v, uint32_t* nb) {
   *nb = v < 144 ? 8u : 9u;
   return v < 144 ? huff(0x30 + v, 8) : huff(0x190 + (v - 144), 9);
 }
+// The length code of 3..258 bytes less 257 (0..28), the number of its extra bits and their value;
+// the distance code of 1..32768 (0..29) likewise.  The fixed coder, the histogram and the dynamic
+// coder share them.
+ZH_BS_HD uint32_t len_code(uint32_t len, uint32_t* eb, uint32_t* ex) {
+  const uint32_t l = len - 3;
+  uint32_t le = l < 8 ? 0 : highbit32(l) - 2;
+  uint32_t lc = 4 * le + (l >> le);
+  uint32_t lx = l & ((1u << le) - 1);
+  if (len == kMaxMatch) lc = 28, le = 0, lx = 0;  // code 285
+  *eb = le, *ex = lx;
+  return lc;
+}
+ZH_BS_HD uint32_t dist_code(uint32_t dist, uint32_t* eb, uint32_t* ex) {
+  const uint32_t d = dist - 1;
+  const uint32_t de = d < 4 ? 0 : highbit32(d) - 1;
+  *eb = de, *ex = d & ((1u << de) - 1);
+  return 2 * de + (d >> de);
+}
 // (bits, count) of a match of 3..258 bytes at a distance of 1..32768: the length code
 // (257..279: 7 bits from 0; 280..287: 8 bits from 0xC0), its extra bits, the 5-bit distance code,
 // its extra bits: 31 bits at the most.
 ZH_BS_HD uint32_t match_bits(uint32_t len, uint32_t dist, uint32_t* nb) {
-  const uint32_t l = len - 3;
-  uint32_t le = l < 8 ? 0 : highbit32(l) - 2;
-  uint32_t lc = 4 * le + (l >> le);  // the code - 257
-  uint32_t lx = l & ((1u << le) - 1);
-  if (len == kMaxMatch) lc = 28, le = 0, lx = 0;  // code 285
-  const uint32_t d = dist - 1;
-  const uint32_t de = d < 4 ? 0 : highbit32(d) - 1;
-  const uint32_t dc = 2 * de + (d >> de);
-  const uint32_t dx = d & ((1u << de) - 1);
+  uint32_t le, lx, de, dx;
+  const uint32_t lc = len_code(len, &le, &lx);
+  const uint32_t dc = dist_code(dist, &de, &dx);
   uint32_t v, k;
   if (lc < 23) {
     v = huff(lc + 1, 7), k = 7;
@@ -252,6 +271,343 @@ ZH_BS_HD uint32_t deflate_block(const uint8_t* s, uint32_t n, const uint16_t* se
   return b.over ? stored : b.o;
 }
 
+// ---- phase 2, the dynamic form ----------------------------------------------------------------
+// Every rule of the dynamic form is stated here once, over a lane policy W (lane, W::n lanes,
+// order(), sum()): the host runs it on OneLane, the device on a wave.  The steps marked "first
+// lane" are short serial chains; the rest is spread over the lanes.
+constexpr uint32_t kLitLen = 286, kDist = 30, kSyms = kLitLen + kDist, kClSyms = 19;
+constexpr uint32_t kEob = 256;
+constexpr uint32_t kMaxCount = 1u << 22;  // code_lengths sorts keys of count << 9 | symbol
+
+// What one block's dynamic form needs: 7 244 bytes, in the wave's LDS on the device.
+struct DynWork {
+  uint32_t hist[kSyms];  // literal/length symbols 0..285, then the distance codes 0..29
+  uint32_t tab[kSyms];   // per symbol: the code as the stream takes it | its length << 16
+  uint32_t a[kLitLen];   // code_lengths: the keys of the used symbols, then the nodes' weights
+  uint32_t b[kLitLen];   // code_lengths: the keys in ascending order
+  uint32_t clhist[kClSyms], cltab[kClSyms];
+  uint32_t cnt[16], next[16];  // codes per length, first code per length
+  uint16_t par[2 * kLitLen];   // code_lengths: a node's parent, then its depth
+  uint16_t items[kSyms];       // the header's code-length symbols: symbol | extra value << 5
+  uint8_t lens[kSyms], cllens[kClSyms + 1];
+  uint32_t used, ok, nitems, hlit, hdist, hclen, fixed_bits, dyn_bits, offered;
+};
+static_assert(sizeof(DynWork) == 7244, "the LDS budget of gzip_deflate_dyn_kernel");
+
+struct OneLane {
+  uint32_t lane = 0;
+  static constexpr uint32_t n = 1;
+  ZH_BS_HD void order() {}
+  ZH_BS_HD uint32_t sum(uint32_t v) { return v; }
+};
+
+ZH_BS_HD uint32_t len_extra(uint32_t lc) { return lc < 8 || lc == 28 ? 0 : (lc >> 2) - 1; }
+ZH_BS_HD uint32_t dist_extra(uint32_t dc) { return dc < 4 ? 0 : (dc >> 1) - 1; }
+// the extra bits behind symbol s of DynWork::hist
+ZH_BS_HD uint32_t sym_extra(uint32_t s) {
+  return s <= kEob ? 0 : s < kLitLen ? len_extra(s - 257) : dist_extra(s - kLitLen);
+}
+ZH_BS_HD uint32_t cl_extra(uint32_t s) { return s == 16 ? 2 : s == 17 ? 3 : s == 18 ? 7 : 0; }
+// the order the code-length code's lengths are sent in: 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2
+// 14 1 15, five bits each
+ZH_BS_HD uint32_t cl_order(uint32_t i) {
+  constexpr uint64_t lo = 16ull | 17ull << 5 | 18ull << 10 | 0ull << 15 | 8ull << 20 | 7ull << 25 |
+                          9ull << 30 | 6ull << 35 | 10ull << 40 | 5ull << 45 | 11ull << 50 |
+                          4ull << 55;
+  constexpr uint64_t hi =
+      12ull | 3ull << 5 | 13ull << 10 | 2ull << 15 | 14ull << 20 | 1ull << 25 | 15ull << 30;
+  return (uint32_t)((i < 12 ? lo >> (5 * i) : hi >> (5 * (i - 12))) & 31u);
+}
+// the table entry of symbol s under the fixed codes of RFC 1951 §3.2.6
+ZH_BS_HD uint32_t fixed_entry(uint32_t s) {
+  if (s < 144) return huff(0x30 + s, 8) | 8u << 16;
+  if (s < 256) return huff(0x190 + (s - 144), 9) | 9u << 16;
+  if (s < 280) return huff(s - 256, 7) | 7u << 16;
+  if (s < kLitLen) return huff(0xC0 + (s - 280), 8) | 8u << 16;
+  return huff(s - kLitLen, 5) | 5u << 16;
+}
+// (bits, count) of a symbol with table entry t followed by eb extra bits of value ex: 28 at most
+ZH_BS_HD uint32_t entry_bits(uint32_t t, uint32_t ex, uint32_t eb, uint32_t* nb) {
+  *nb = (t >> 16) + eb;
+  return (t & 0xFFFFu) | ex << (t >> 16);
+}
+
+// The code lengths of a Huffman code over the symbols with counts[s] > 0 (counts <= kMaxCount,
+// nsym <= 286, limit <= 15), none longer than `limit`: a pure function of the counts.
+//   * no symbol used: all lengths 0; one used: that symbol gets length 1;
+//   * the used symbols in ascending order of (count, symbol); Huffman's merge with two queues,
+//     the leaves and the nodes made so far, a leaf before a node of equal weight: an optimal code;
+//   * only the number of leaves at each depth is kept.  Depths past `limit` are folded into
+//     `limit`; while the Kraft sum is above 1, the deepest leaf above row `limit` moves down one
+//     row and a leaf of row `limit` moves up beside it, which takes 2^-limit off the sum;
+//   * the lengths go out in the sorted order, the longest to the rarest: no symbol has a longer
+//     code than a rarer one, and of two equally frequent symbols the lower has the longer code.
+// False when no such code exists or an argument is out of range (never, from the callers here).
+template <class W>
+ZH_BS_HD bool code_lengths(const uint32_t* counts, uint32_t nsym, uint32_t limit, uint8_t* lens,
+                           DynWork& d, W& w) {
+  if (nsym > kLitLen || limit < 1 || limit > 15) return false;
+  for (uint32_t s = w.lane; s < nsym; s += W::n) lens[s] = 0;
+  if (w.lane == 0) {  // first lane: the keys of the used symbols
+    uint32_t u = 0;
+    bool ok = true;
+    for (uint32_t s = 0; s < nsym; s++) {
+      const uint32_t c = counts[s];
+      if (c > kMaxCount) ok = false;
+      if (c && ok) d.a[u++] = c << 9 | s;
+    }
+    d.used = u;
+    d.ok = ok;
+  }
+  w.order();
+  const uint32_t u = d.used;
+  if (!d.ok || u > (1u << limit)) return false;
+  if (u == 0) return true;
+  if (u == 1) {
+    if (w.lane == 0) lens[d.a[0] & 511u] = 1;
+    w.order();
+    return true;
+  }
+  for (uint32_t i = w.lane; i < u; i += W::n) {  // the keys differ: a key's rank is its place
+    const uint32_t key = d.a[i];
+    uint32_t r = 0;
+    for (uint32_t j = 0; j < u; j++) r += d.a[j] < key ? 1u : 0u;
+    d.b[r] = key;
+  }
+  w.order();
+  if (w.lane == 0) {  // first lane: leaves 0..u-1 in sorted order, node m is u + m, weight a[m]
+    uint32_t li = 0, ii = 0;
+    for (uint32_t m = 0; m + 1 < u; m++) {
+      uint32_t sum = 0;
+      for (int t = 0; t < 2; t++) {
+        if (li < u && (ii >= m || (d.b[li] >> 9) <= d.a[ii])) {
+          sum += d.b[li] >> 9;
+          d.par[li++] = (uint16_t)(u + m);
+        } else {
+          sum += d.a[ii];
+          d.par[u + ii++] = (uint16_t)(u + m);
+        }
+      }
+      d.a[m] = sum;
+    }
+    for (uint32_t bl = 0; bl < 16; bl++) d.cnt[bl] = 0;
+    d.par[2 * u - 2] = 0;  // the root; a parent comes after its children
+    uint32_t kraft = 0;    // in units of 2^-limit
+    for (uint32_t v = 2 * u - 2; v-- > 0;) {
+      const uint32_t dep = d.par[d.par[v]] + 1u;
+      d.par[v] = (uint16_t)dep;
+      if (v < u) {
+        const uint32_t bl = dep < limit ? dep : limit;
+        d.cnt[bl]++;
+        kraft += 1u << (limit - bl);
+      }
+    }
+    bool ok = true;
+    while (ok && kraft > (1u << limit)) {
+      uint32_t bl = limit - 1;
+      while (bl > 0 && d.cnt[bl] == 0) bl--;
+      if (bl == 0 || d.cnt[limit] == 0) {
+        ok = false;  // never: u <= 2^limit
+        break;
+      }
+      d.cnt[bl]--, d.cnt[bl + 1] += 2, d.cnt[limit]--, kraft--;
+    }
+    uint32_t i = 0;
+    for (uint32_t bl = limit; ok && bl >= 1; bl--)
+      for (uint32_t c = d.cnt[bl]; c > 0 && i < u; c--) lens[d.b[i++] & 511u] = (uint8_t)bl;
+    d.ok = ok && i == u && kraft == (1u << limit);
+  }
+  w.order();
+  return d.ok != 0;
+}
+
+// First lane: the canonical codes (RFC 1951 §3.2.2) of nsym lengths into tab.
+ZH_BS_HD void make_codes(const uint8_t* lens, uint32_t nsym, uint32_t* tab, DynWork& d) {
+  for (uint32_t bl = 0; bl < 16; bl++) d.cnt[bl] = 0;
+  for (uint32_t s = 0; s < nsym; s++) d.cnt[lens[s]]++;
+  d.cnt[0] = 0;
+  uint32_t code = 0;
+  d.next[0] = 0;
+  for (uint32_t bl = 1; bl < 16; bl++) d.next[bl] = code = (code + d.cnt[bl - 1]) << 1;
+  for (uint32_t s = 0; s < nsym; s++) {
+    const uint32_t bl = lens[s];
+    tab[s] = bl ? huff(d.next[bl]++, bl) | bl << 16 : 0u;
+  }
+}
+
+// The lengths the header describes, literal/length lengths first: runs cross the seam.
+ZH_BS_HD uint32_t header_len(const DynWork& d, uint32_t hlit, uint32_t i) {
+  return d.lens[i < hlit ? i : kLitLen + (i - hlit)];
+}
+ZH_BS_HD void header_item(DynWork& d, uint32_t sym, uint32_t ex) {
+  d.items[d.nitems++] = (uint16_t)(sym | ex << 5);
+  d.clhist[sym]++;
+}
+
+// From the block's histogram (hist; the end-of-block counted): the code lengths of both sets,
+// the header, and the exact bits of the fixed and the dynamic form, each from its three header
+// bits to its end-of-block code.
+//   * the literal/length set holds two used symbols or more (a literal or a length, and the
+//     end of block): it is complete.  One used distance code has length 1; no match: HDIST 0 and
+//     one length of 0;
+//   * HLIT and HDIST lose their trailing zero lengths; the HLIT + 257 + HDIST + 1 lengths are one
+//     sequence, coded greedily: zero runs of 11..138 are symbol 18, of 3..10 symbol 17; another
+//     length is sent once and its repeats in runs of 3..6 as symbol 16; what is left is sent
+//     plain;
+//   * the code-length code has at most 7 bits; HCLEN loses its trailing zeros in cl_order.  A
+//     code-length code of one symbol is incomplete and zlib rejects it: the form is then not
+//     offered (never: every header holds a length and something else).
+template <class W>
+ZH_BS_HD void plan_dynamic(DynWork& d, W& w) {
+  uint32_t fx = 0;
+  for (uint32_t s = w.lane; s < kSyms; s += W::n)
+    fx += d.hist[s] * ((fixed_entry(s) >> 16) + sym_extra(s));
+  fx = w.sum(fx);
+  bool ok = code_lengths(d.hist, kLitLen, 15, d.lens, d, w);
+  ok = code_lengths(d.hist + kLitLen, kDist, 15, d.lens + kLitLen, d, w) && ok;
+  uint32_t dy = 0;
+  for (uint32_t s = w.lane; s < kSyms; s += W::n) dy += d.hist[s] * (d.lens[s] + sym_extra(s));
+  dy = w.sum(dy);
+  if (w.lane == 0) {  // first lane: the header's symbols
+    uint32_t hlit = kLitLen, hdist = kDist;
+    while (hlit > 257 && d.lens[hlit - 1] == 0) hlit--;
+    while (hdist > 1 && d.lens[kLitLen + hdist - 1] == 0) hdist--;
+    d.hlit = hlit, d.hdist = hdist, d.nitems = 0;
+    for (uint32_t s = 0; s < kClSyms; s++) d.clhist[s] = 0;
+    const uint32_t total = hlit + hdist;
+    for (uint32_t i = 0; i < total;) {
+      const uint32_t v = header_len(d, hlit, i);
+      uint32_t run = 1;
+      while (i + run < total && header_len(d, hlit, i + run) == v) run++;
+      i += run;
+      if (v == 0) {
+        for (uint32_t t; run >= 11; run -= t) header_item(d, 18, (t = run < 138 ? run : 138) - 11);
+        if (run >= 3) header_item(d, 17, run - 3), run = 0;
+      } else {
+        header_item(d, v, 0);
+        run--;
+        for (uint32_t t; run >= 3; run -= t) header_item(d, 16, (t = run < 6 ? run : 6) - 3);
+      }
+      for (; run; run--) header_item(d, v, 0);
+    }
+  }
+  w.order();
+  ok = code_lengths(d.clhist, kClSyms, 7, d.cllens, d, w) && ok;
+  if (w.lane == 0) {
+    uint32_t hclen = kClSyms, hdr = 0, clused = 0;
+    while (hclen > 4 && d.cllens[cl_order(hclen - 1)] == 0) hclen--;
+    for (uint32_t s = 0; s < kClSyms; s++) {
+      hdr += d.clhist[s] * (d.cllens[s] + cl_extra(s));
+      clused += d.clhist[s] ? 1u : 0u;
+    }
+    d.hclen = hclen;
+    d.fixed_bits = 3 + fx;
+    d.dyn_bits = 3 + 14 + 3 * hclen + hdr + dy;
+    d.offered = ok && clused >= 2 ? 1u : 0u;
+  }
+  w.order();
+}
+
+// The bytes of a fixed or dynamic segment of `bits` bits up to its end-of-block code: the three
+// marker bits, zero bits to the byte boundary, 00 00 ff ff.
+ZH_BS_HD uint32_t segment_bytes(uint32_t bits) { return (bits + 3 + 7) / 8 + 4; }
+
+// The form of the block's segment and its size: the smallest of stored (0), fixed (1) and
+// dynamic (2); stored wins a tie, fixed wins one against dynamic.
+ZH_BS_HD uint32_t choose_form(uint32_t n, const DynWork& d, uint32_t* size) {
+  uint32_t form = 0;
+  *size = n + kStoredOver;
+  if (segment_bytes(d.fixed_bits) < *size) form = 1, *size = segment_bytes(d.fixed_bits);
+  if (d.offered && segment_bytes(d.dyn_bits) < *size) form = 2, *size = segment_bytes(d.dyn_bits);
+  return form;
+}
+
+// The (code, length) tables of the chosen form into d.tab (and d.cltab).
+template <class W>
+ZH_BS_HD void form_tables(uint32_t form, DynWork& d, W& w) {
+  if (form == 1) {
+    for (uint32_t s = w.lane; s < kSyms; s += W::n) d.tab[s] = fixed_entry(s);
+  } else if (w.lane == 0) {
+    make_codes(d.lens, kLitLen, d.tab, d);
+    make_codes(d.lens + kLitLen, kDist, d.tab + kLitLen, d);
+    make_codes(d.cllens, kClSyms, d.cltab, d);
+  }
+  w.order();
+}
+
+// The host's histogram walk: every literal, the length code of every piece and its distance
+// code, one end-of-block.  False when the records do not partition the block (never).
+inline bool hist_block(const uint8_t* s, uint32_t n, const uint16_t* seq, uint32_t ns,
+                       DynWork& d) {
+  for (uint32_t i = 0; i < kSyms; i++) d.hist[i] = 0;
+  uint32_t pos = 0;
+  for (uint32_t k = 0; k <= ns; k++) {
+    const uint32_t lit = k < ns ? seq[3 * k] : n - pos;
+    if (lit > n - pos) return false;
+    for (uint32_t i = 0; i < lit; i++) d.hist[s[pos + i]]++;
+    pos += lit;
+    if (k == ns) break;
+    const uint32_t ml = seq[3 * k + 1], off = seq[3 * k + 2];
+    if (ml < kMinPiece || ml > n - pos || off == 0 || off > pos) return false;
+    uint32_t eb, ex;
+    for (uint32_t j = 0, np = piece_count(ml); j < np; j++)
+      d.hist[257 + len_code(piece_len(ml, j), &eb, &ex)]++;
+    d.hist[kLitLen + dist_code(off, &eb, &ex)] += piece_count(ml);
+    pos += ml;
+  }
+  d.hist[kEob] = 1;
+  return true;
+}
+
+// deflate_block with the dynamic form in the choice: the size of the block's segment, written
+// to out (room for n + 4 bytes) unless it is stored.  The sizes are known before a bit is
+// written; the fixed form comes out of the same table walk as the dynamic one.
+inline uint32_t deflate_block_dynamic(const uint8_t* s, uint32_t n, const uint16_t* seq,
+                                      uint32_t ns, uint32_t covered, uint8_t* out, DynWork& d) {
+  const uint32_t stored = n + kStoredOver;
+  if (covered > n || !hist_block(s, n, seq, ns, d)) return stored;
+  OneLane w;
+  plan_dynamic(d, w);
+  uint32_t size = 0, nb = 0;
+  const uint32_t form = choose_form(n, d, &size);
+  if (form == 0) return stored;
+  form_tables(form, d, w);
+  BitOut b{out, 0, stored - 1};
+  b.add(form == 2 ? 4 : 2, 3);  // BFINAL 0, BTYPE 10 or 01
+  if (form == 2) {
+    b.add((d.hlit - 257) | (d.hdist - 1) << 5 | (d.hclen - 4) << 10, 14);
+    for (uint32_t i = 0; i < d.hclen; i++) b.add(d.cllens[cl_order(i)], 3);
+    for (uint32_t i = 0; i < d.nitems; i++) {
+      const uint32_t sym = d.items[i] & 31u;
+      const uint32_t v = entry_bits(d.cltab[sym], d.items[i] >> 5, cl_extra(sym), &nb);
+      b.add(v, nb);
+    }
+  }
+  uint32_t pos = 0;
+  for (uint32_t k = 0; k <= ns; k++) {
+    const uint32_t lit = k < ns ? seq[3 * k] : n - pos;
+    for (uint32_t i = 0; i < lit; i++) b.add(d.tab[s[pos + i]] & 0xFFFFu, d.tab[s[pos + i]] >> 16);
+    pos += lit;
+    if (k == ns) break;
+    const uint32_t ml = seq[3 * k + 1], off = seq[3 * k + 2];
+    for (uint32_t j = 0, np = piece_count(ml); j < np; j++) {
+      uint32_t eb, ex;
+      const uint32_t lc = len_code(piece_len(ml, j), &eb, &ex);
+      uint32_t v = entry_bits(d.tab[257 + lc], ex, eb, &nb);
+      b.add(v, nb);
+      const uint32_t dc = dist_code(off, &eb, &ex);
+      v = entry_bits(d.tab[kLitLen + dc], ex, eb, &nb);
+      b.add(v, nb);
+    }
+    pos += ml;
+  }
+  b.add(d.tab[kEob] & 0xFFFFu, d.tab[kEob] >> 16);
+  b.add(0, 3);  // the marker: BFINAL 0, BTYPE 00
+  if (b.cnt) b.add(0, 8 - b.cnt);
+  b.add(0xFFFF0000u, 32);  // LEN 0, NLEN ffff
+  return b.over || b.o != size ? stored : b.o;  // never stored here: the sizes are exact
+}
+
 // ---- member layout --------------------------------------------------------------------------
 inline size_t block_count(size_t n, uint32_t B) { return (n + B - 1) / B; }
 inline uint32_t block_size(size_t n, uint32_t B, size_t k) {
@@ -276,11 +632,17 @@ inline uint32_t stored_word(uint32_t len) { return len | ((~len & 0xFFFFu) << 16
 
 struct Params {
   uint32_t B = kDefaultBlock;
+  bool dynamic = false;
 };
 inline bool read_params(const zh_gzip_enc_params* p, Params* out) {
-  if (!p || p->blocksize < 0) return false;
+  if (!p || p->blocksize < 0 || (p->dynamic != 0 && p->dynamic != 1)) return false;
   out->B = block_bytes(p->blocksize);
+  out->dynamic = p->dynamic == 1;
   return true;
+}
+// read_params refused the `dynamic` field, not the block size
+inline bool bad_dynamic(const zh_gzip_enc_params* p) {
+  return p && p->blocksize >= 0 && p->dynamic != 0 && p->dynamic != 1;
 }
 
 // One member on the host with HostLanes.  dst == nullptr: *len = the bound.
@@ -288,7 +650,8 @@ inline int compress_member(const uint8_t* src, size_t n, const zh_gzip_enc_param
                            uint8_t* dst, size_t cap, size_t* len, const char** msg) {
   Params P;
   if (!read_params(prm, &P) || (n > 0 && !src) || !len) {
-    *msg = "zh_gzip_compress: blocksize >= 0";
+    *msg = bad_dynamic(prm) ? "zh_gzip_compress: dynamic is 0 or 1"
+                            : "zh_gzip_compress: blocksize >= 0";
     return ZH_EINVAL;
   }
   const size_t bound = member_bound(n, P.B);
@@ -304,6 +667,7 @@ inline int compress_member(const uint8_t* src, size_t n, const zh_gzip_enc_param
   uint8_t* seg = new uint8_t[P.B + kStoredOver];
   uint16_t* seq = new uint16_t[3 * (size_t)(P.B / 4) + 3];
   uint32_t* table = new uint32_t[zh_lz::kHashSize];
+  DynWork* dyn = P.dynamic ? new DynWork : nullptr;
   zh_lz::HostLanes w;
   w.wide = true;
   put_header(dst);
@@ -313,7 +677,8 @@ inline int compress_member(const uint8_t* src, size_t n, const zh_gzip_enc_param
     const uint8_t* s = src + k * P.B;
     uint32_t covered = 0;
     const uint32_t ns = match_block(s, bsz, seq, table, w, &covered);
-    const uint32_t size = deflate_block(s, bsz, seq, ns, covered, seg);
+    const uint32_t size = dyn ? deflate_block_dynamic(s, bsz, seq, ns, covered, seg, *dyn)
+                              : deflate_block(s, bsz, seq, ns, covered, seg);
     if (size == bsz + kStoredOver) {
       const uint32_t word = stored_word(bsz);
       dst[p++] = 0;
@@ -327,6 +692,7 @@ inline int compress_member(const uint8_t* src, size_t n, const zh_gzip_enc_param
   }
   put_ending(dst + p, crc_finish(crc_raw(0, src, n), n), n);
   p += kEnding + kTrailer;
+  delete dyn;
   delete[] table;
   delete[] seq;
   delete[] seg;

@@ -25,6 +25,9 @@
 //           stored size) goes to a table.  The kernel boundary orders the records.  The form
 //           with one thread per block that was built first took 113 ms where the match kernel
 //           took 5.9 ms (DESIGN.md "Gzip members encoded on the device").
+//   gzip_deflate_dyn_kernel<CAP, WAVES>   its sibling for zh_gzip_enc_params::dynamic = 1, the
+//           wave form of zh_gz::deflate_block_dynamic (described at the kernel): a zh_gz::DynWork
+//           in LDS per wave, 160 112 B per workgroup at 16 KiB;
 //   host    one small copy brings the size table back; a prefix sum lays the members out and
 //           builds the copy jobs;
 //   blosc_gather_kernel (zh_enc_device.h)   one workgroup per job: headers and endings from the
@@ -40,6 +43,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <new>
 #include <vector>
 
 #include "zh_ctx.h"
@@ -163,6 +167,35 @@ struct WaveCoder {
     if (nb) bits(bitpos + incl - nb, v, nb);
     bitpos += total;
   }
+  // put() for symbols of up to 64 bits: the two halves of a match under the dynamic codes
+  __device__ void put64(uint64_t v, uint32_t nb) {
+    uint32_t incl = nb;
+    for (int d = 1; d < 64; d *= 2) {
+      const uint32_t y = (uint32_t)__shfl_up((int)incl, d);
+      if (lane >= (uint32_t)d) incl += y;
+    }
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    if (bitpos + total > limit) {
+      over = true;
+      return;
+    }
+    const uint32_t at = bitpos + incl - nb;
+    if (nb) bits(at, (uint32_t)v, nb < 32u ? nb : 32u);
+    if (nb > 32) bits(at + 32, (uint32_t)(v >> 32), nb - 32);
+    bitpos += total;
+  }
+};
+
+// The wave as the lane policy of the dynamic form's rules (zh_gzip_enc.h): 64 lanes, the wave's
+// LDS ordered between the steps, a butterfly sum.
+struct WaveDyn {
+  uint32_t lane;
+  static constexpr uint32_t n = 64;
+  __device__ void order() { WaveLanes::order(); }
+  __device__ uint32_t sum(uint32_t v) {
+    for (int d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    return v;
+  }
 };
 
 template <uint32_t CAP, int WAVES>
@@ -251,6 +284,197 @@ __global__ __launch_bounds__(WAVES * 64) void gzip_deflate_kernel(
   for (uint32_t i = lane; i < (bytes + 4 + 3) / 4; i += 64) out[i] = win[i];
 }
 
+// gzip_deflate_kernel with the dynamic form in the choice, the wave form of
+// zh_gz::deflate_block_dynamic: next to the block and its window the wave has a zh_gz::DynWork in
+// LDS.  Four steps:
+//   histogram   the records 64 at a time (each lane the pieces of its own match) and the literals
+//               64 at a time, added into the 316 counters with LDS atomics;
+//   codes       zh_gz::plan_dynamic: the code lengths (the keys ranked by all lanes, the merge,
+//               the depths and the header's run-length coding on the first lane), the exact sizes;
+//   choice      zh_gz::choose_form, then the (code, length) tables of the form chosen: the fixed
+//               codes are one such table, so one walk writes either form;
+//   coding      the header's symbols 64 at a time and the block's symbols as in
+//               gzip_deflate_kernel, looked up in the tables; the code lengths vary, so 64
+//               literals take a wave scan; a match of one piece is two symbols from the first
+//               lane.
+// WaveLanes::order() stands between the atomics and every read of the counters, and between the
+// first lane's tables and their readers (inside the shared steps).
+template <uint32_t CAP, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void gzip_deflate_dyn_kernel(
+    const GBlock* __restrict__ blocks, uint32_t nblocks, uint8_t* __restrict__ scratch,
+    const uint16_t* __restrict__ seqs, const uint32_t* __restrict__ info,
+    uint32_t* __restrict__ csize) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[WAVES][CAP];
+  __shared__ uint32_t wins[WAVES][CAP / 4 + 4];
+  __shared__ zh_gz::DynWork works[WAVES];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t k = blockIdx.x * WAVES + wave;
+  if (k >= nblocks) return;  // the whole wave: the kernel has no barrier
+  const GBlock b = blocks[k];
+  const uint32_t n = b.size, stored = n + zh_gz::kStoredOver;
+  const uint32_t ns = info[2 * k], covered = info[2 * k + 1];
+  if (n > CAP || ns > n / zh_lz::kMinMatch || covered > n) {
+    if (lane == 0) csize[k] = stored;
+    return;
+  }
+  uint8_t* blk = lds[wave];
+  uint32_t* win = wins[wave];
+  zh_gz::DynWork& d = works[wave];
+  load_block(blk, (const uint8_t*)b.src, n, lane);
+  const uint32_t nwin = (n + 4) / 4 + 2;  // n + 4 bytes and the word a symbol may reach into
+  for (uint32_t i = lane; i < nwin; i += 64) win[i] = 0;
+  for (uint32_t i = lane; i < zh_gz::kSyms; i += 64) d.hist[i] = 0;
+  WaveLanes::order();
+  const uint16_t* __restrict__ sq = seqs + b.seq;
+
+  // the histogram, and the tests of zh_gz::hist_block
+  bool bad = false;
+  uint32_t pos = 0;
+  for (uint32_t k0 = 0; k0 <= ns && !bad; k0 += 64) {
+    uint32_t r_lit = 0, r_ml = 0, r_off = 0;
+    if (k0 + lane < ns) {
+      r_lit = sq[3 * (k0 + lane)];
+      r_ml = sq[3 * (k0 + lane) + 1];
+      r_off = sq[3 * (k0 + lane) + 2];
+    }
+    // a record the walk below refuses is not counted: its codes may lie outside the counters
+    if (r_ml >= zh_gz::kMinPiece && r_off >= 1 && r_off <= zh_gz::kMaxBlock) {
+      uint32_t eb, ex;
+      const uint32_t np = zh_gz::piece_count(r_ml);
+      for (uint32_t j = 0; j < np; j++)
+        atomicAdd(&d.hist[257 + zh_gz::len_code(zh_gz::piece_len(r_ml, j), &eb, &ex)], 1u);
+      atomicAdd(&d.hist[zh_gz::kLitLen + zh_gz::dist_code(r_off, &eb, &ex)], np);
+    }
+    const uint32_t cnt = ns + 1 - k0 < 64u ? ns + 1 - k0 : 64u;
+    for (uint32_t j = 0; j < cnt; j++) {
+      const bool last = k0 + j == ns;
+      const uint32_t lit = last ? n - pos : (uint32_t)__builtin_amdgcn_readlane((int)r_lit, j);
+      const uint32_t ml = (uint32_t)__builtin_amdgcn_readlane((int)r_ml, j);
+      const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)r_off, j);
+      if (lit > n - pos) {  // never: the records partition the block
+        bad = true;
+        break;
+      }
+      for (uint32_t i0 = 0; i0 < lit; i0 += 64)
+        if (i0 + lane < lit) atomicAdd(&d.hist[blk[pos + i0 + lane]], 1u);
+      pos += lit;
+      if (last) break;
+      if (ml < zh_gz::kMinPiece || ml > n - pos || off == 0 || off > pos) {  // never
+        bad = true;
+        break;
+      }
+      pos += ml;
+    }
+  }
+  if (bad) {
+    if (lane == 0) csize[k] = stored;
+    return;
+  }
+  if (lane == 0) d.hist[zh_gz::kEob] = 1;  // no atomic adds to it
+  WaveLanes::order();
+
+  WaveDyn w{lane};
+  zh_gz::plan_dynamic(d, w);
+  uint32_t size = 0;
+  const uint32_t form = zh_gz::choose_form(n, d, &size);
+  if (form == 0) {
+    if (lane == 0) csize[k] = stored;
+    return;
+  }
+  zh_gz::form_tables(form, d, w);
+
+  // The sizes are exact.  Here the header bits and the end-of-block code go through the coder
+  // too (gzip_deflate_kernel adds its end-of-block code outside): size <= n + 4 means
+  // ceil((bits + 3) / 8) <= n, so all of them end at 8 n - 3 bits or before, inside the window.
+  WaveCoder c{win, lane, 0, 8 * n - 3};
+  c.one(form == 2 ? 4u : 2u, 3);  // BFINAL 0, BTYPE 10 or 01
+  if (form == 2) {
+    c.one((d.hlit - 257) | (d.hdist - 1) << 5 | (d.hclen - 4) << 10, 14);
+    c.put(lane < d.hclen ? d.cllens[zh_gz::cl_order(lane)] : 0u, lane < d.hclen ? 3u : 0u);
+    for (uint32_t i0 = 0; i0 < d.nitems && !c.over; i0 += 64) {
+      uint32_t v = 0, nb = 0;
+      if (i0 + lane < d.nitems) {
+        const uint32_t it = d.items[i0 + lane], sym = it & 31u;
+        v = zh_gz::entry_bits(d.cltab[sym], it >> 5, zh_gz::cl_extra(sym), &nb);
+      }
+      c.put(v, nb);
+    }
+  }
+  pos = 0;
+  for (uint32_t k0 = 0; k0 <= ns && !c.over; k0 += 64) {  // record ns: the literals at the end
+    uint32_t r_lit = 0, r_ml = 0, r_off = 0;
+    if (k0 + lane < ns) {
+      r_lit = sq[3 * (k0 + lane)];
+      r_ml = sq[3 * (k0 + lane) + 1];
+      r_off = sq[3 * (k0 + lane) + 2];
+    }
+    const uint32_t cnt = ns + 1 - k0 < 64u ? ns + 1 - k0 : 64u;
+    for (uint32_t j = 0; j < cnt && !c.over; j++) {
+      const bool last = k0 + j == ns;
+      const uint32_t lit = last ? n - pos : (uint32_t)__builtin_amdgcn_readlane((int)r_lit, j);
+      const uint32_t ml = (uint32_t)__builtin_amdgcn_readlane((int)r_ml, j);
+      const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)r_off, j);
+      for (uint32_t i0 = 0; i0 < lit && !c.over; i0 += 64) {
+        const uint32_t t = i0 + lane < lit ? d.tab[blk[pos + i0 + lane]] : 0u;
+        c.put(t & 0xFFFFu, t >> 16);
+      }
+      pos += lit;
+      if (last || c.over) break;
+      uint32_t eb, ex, nb1, nb2;
+      const uint32_t dc = zh_gz::dist_code(off, &eb, &ex);
+      const uint32_t v2 = zh_gz::entry_bits(d.tab[zh_gz::kLitLen + dc], ex, eb, &nb2);
+      const uint32_t np = zh_gz::piece_count(ml);
+      if (np == 1) {
+        const uint32_t lc = zh_gz::len_code(ml, &eb, &ex);
+        const uint32_t v1 = zh_gz::entry_bits(d.tab[257 + lc], ex, eb, &nb1);
+        c.one(v1, nb1);
+        if (!c.over) c.one(v2, nb2);
+      }
+      for (uint32_t p0 = 0; np > 1 && p0 < np && !c.over; p0 += 64) {
+        uint64_t v = 0;
+        uint32_t nb = 0;
+        if (p0 + lane < np) {
+          const uint32_t lc = zh_gz::len_code(zh_gz::piece_len(ml, p0 + lane), &eb, &ex);
+          const uint32_t v1 = zh_gz::entry_bits(d.tab[257 + lc], ex, eb, &nb1);
+          v = v1 | (uint64_t)v2 << nb1;
+          nb = nb1 + nb2;
+        }
+        c.put64(v, nb);
+      }
+      pos += ml;
+    }
+  }
+  if (!c.over) c.one(d.tab[zh_gz::kEob] & 0xFFFFu, d.tab[zh_gz::kEob] >> 16);
+  const uint32_t bytes = (c.bitpos + 3 + 7) / 8;  // marker bits, zero bits
+  if (c.over || bytes + 4 != size) {              // never: the sizes are exact
+    if (lane == 0) csize[k] = stored;
+    return;
+  }
+  if (lane == 0) {
+    c.bits(8 * (bytes + 2), 0xFFFFu, 16);  // LEN 0, NLEN ffff
+    csize[k] = size;
+  }
+  WaveLanes::order();
+  uint32_t* __restrict__ out = (uint32_t*)(scratch + b.out);  // 16-byte aligned, size + 8 long
+  for (uint32_t i = lane; i < (size + 3) / 4; i += 64) out[i] = win[i];
+}
+
+// One wave per histogram: zh_gz::code_lengths as the dynamic coder runs it
+// (zh_debug_gzip_code_lengths).  255: no code.
+__global__ __launch_bounds__(64) void gzip_code_lengths_kernel(const uint32_t* __restrict__ counts,
+                                                               uint32_t nsym, uint32_t limit,
+                                                               uint8_t* __restrict__ lens) {
+  __shared__ zh_gz::DynWork d;
+  const uint32_t lane = threadIdx.x;
+  const size_t row = (size_t)blockIdx.x * nsym;
+  if (nsym > zh_gz::kLitLen) return;
+  for (uint32_t i = lane; i < nsym; i += 64) d.hist[i] = counts[row + i];
+  WaveLanes::order();
+  WaveDyn w{lane};
+  const bool ok = zh_gz::code_lengths(d.hist, nsym, limit, d.lens, d, w);
+  for (uint32_t i = lane; i < nsym; i += 64) lens[row + i] = ok ? d.lens[i] : (uint8_t)255;
+}
+
 __global__ __launch_bounds__(kThreads) void gzip_crc32_kernel(const CrcJob* __restrict__ jobs,
                                                               uint32_t x_piece,
                                                               uint32_t* __restrict__ out) {
@@ -313,10 +537,17 @@ void launch_match(uint32_t B, hipStream_t s, const GBlock* blocks, uint32_t nblo
   }
 }
 
-void launch_deflate(uint32_t B, hipStream_t s, const GBlock* blocks, uint32_t nblocks,
-                    uint8_t* scratch, const uint16_t* seqs, const uint32_t* info,
+void launch_deflate(const zh_gz::Params& P, hipStream_t s, const GBlock* blocks,
+                    uint32_t nblocks, uint8_t* scratch, const uint16_t* seqs, const uint32_t* info,
                     uint32_t* csize) {
-  if (B <= (16u << 10)) {
+  const uint32_t B = P.B;
+  if (P.dynamic && B <= (16u << 10)) {
+    hipLaunchKernelGGL((gzip_deflate_dyn_kernel<(16u << 10), 4>), dim3((nblocks + 3) / 4),
+                       dim3(256), 0, s, blocks, nblocks, scratch, seqs, info, csize);
+  } else if (P.dynamic) {
+    hipLaunchKernelGGL((gzip_deflate_dyn_kernel<zh_gz::kMaxBlock, 2>), dim3((nblocks + 1) / 2),
+                       dim3(128), 0, s, blocks, nblocks, scratch, seqs, info, csize);
+  } else if (B <= (16u << 10)) {
     hipLaunchKernelGGL((gzip_deflate_kernel<(16u << 10), 4>), dim3((nblocks + 3) / 4), dim3(256),
                        0, s, blocks, nblocks, scratch, seqs, info, csize);
   } else {
@@ -390,7 +621,7 @@ int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, const uint32_t* crcs,
                    (uint32_t*)(d8 + o_info));
     if (timed) (void)hipEventRecord(ev[1], s);
     if (nb)
-      launch_deflate(P.B, s, (const GBlock*)(d8 + o_blocks), (uint32_t)nb, d8 + o_scratch,
+      launch_deflate(P, s, (const GBlock*)(d8 + o_blocks), (uint32_t)nb, d8 + o_scratch,
                      (const uint16_t*)(d8 + o_seq), (const uint32_t*)(d8 + o_info),
                      (uint32_t*)(d8 + o_cs));
     if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
@@ -575,7 +806,8 @@ int zh_gzip_encode_batch(zh_ctx* ctx, zh_gzip_enc_frame* frames, int64_t n,
   const int64_t bound = bound_of(frames, n, params);
   if (bound < 0) {
     for (int64_t i = 0; i < n && frames; i++) frames[i].status = ZH_EINVAL;
-    put_err(err, errlen, "gzip encode: blocksize >= 0, sizes >= 0");
+    put_err(err, errlen, zh_gz::bad_dynamic(params) ? "gzip encode: dynamic is 0 or 1"
+                                                    : "gzip encode: blocksize >= 0, sizes >= 0");
     return ZH_EINVAL;
   }
   if (bound > dstcap || (bound > 0 && !dst)) {
@@ -627,6 +859,58 @@ int zh_debug_gzip_crc32(zh_ctx* ctx, const zh_gzip_enc_frame* frames, int64_t n,
   if (rc != ZH_OK) return rc;
   double ms = 0;
   return crc_frames(ctx, ctx->stream, ring, frames, n, out, &ms);
+}
+
+int zh_debug_gzip_code_lengths(zh_ctx* ctx, const uint32_t* counts, int32_t nsym, int32_t limit,
+                               int64_t rows, uint8_t* lens) {
+  if (nsym < 1 || nsym > (int32_t)zh_gz::kLitLen || limit < 1 || limit > 15 || rows < 0 ||
+      rows > ((int64_t)1 << 20) || (rows > 0 && (!counts || !lens)))
+    return ZH_EINVAL;
+  if (rows == 0) return ZH_OK;
+  const size_t total = (size_t)rows * (size_t)nsym;
+  int rc = ZH_OK;
+  if (!ctx) {
+    zh_gz::DynWork* d = new (std::nothrow) zh_gz::DynWork;
+    if (!d) return ZH_ENOMEM;
+    zh_gz::OneLane w;
+    for (int64_t r = 0; r < rows; r++) {
+      uint8_t* out = lens + (size_t)r * (size_t)nsym;
+      if (!zh_gz::code_lengths(counts + (size_t)r * (size_t)nsym, (uint32_t)nsym, (uint32_t)limit,
+                               d->lens, *d, w)) {
+        rc = ZH_EINVAL;
+        memset(out, 255, (size_t)nsym);
+      } else {
+        memcpy(out, d->lens, (size_t)nsym);
+      }
+    }
+    delete d;
+    return rc;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  (void)hipSetDevice(ctx->device);
+  Ring ring;
+  rc = ring.init(ctx, ctx->stream);
+  if (rc != ZH_OK) return rc;
+  const size_t o_lens = (size_t)up((int64_t)(total * 4), 256);
+  void* dmem = nullptr;
+  size_t got = 0;
+  if (zh::ctx_alloc(ctx, o_lens + total, &dmem, &got) != hipSuccess) {
+    (void)hipGetLastError();
+    return ZH_ENOMEM;
+  }
+  uint8_t* d8 = (uint8_t*)dmem;
+  if (!ring.h2d(d8, (const uint8_t*)counts, total * 4)) rc = ZH_EHIP;
+  if (rc == ZH_OK) {
+    hipLaunchKernelGGL(gzip_code_lengths_kernel, dim3((unsigned)rows), dim3(64), 0, ctx->stream,
+                       (const uint32_t*)d8, (uint32_t)nsym, (uint32_t)limit, d8 + o_lens);
+    if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
+  }
+  if (rc == ZH_OK && !ring.d2h(lens, d8 + o_lens, total)) rc = ZH_EHIP;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
+  zh::ctx_release(ctx, dmem, got);
+  for (size_t i = 0; rc == ZH_OK && i < total; i++)
+    if (lens[i] == 255) rc = ZH_EINVAL;
+  return rc;
 }
 
 }  // extern "C"

@@ -3,8 +3,9 @@
 //
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 //       -o gzip_enc_check tools/gzip_enc_check.cpp -lz
-//   gzip_enc_check buffers.bin members.bin
+//   gzip_enc_check buffers.bin members.bin [dynamic]
 //
+// dynamic (0 or 1, default 0): zh_gzip_enc_params::dynamic for every buffer.
 // buffers.bin: per buffer two little-endian uint32 (length, blocksize) and the bytes.  Every
 // buffer is compressed with the host form of the writer (the lane loop the kernel runs as one
 // wave, the serial coder whose wave form the second kernel is), decoded again with zlib's inflate
@@ -67,10 +68,11 @@ static bool inflate_gzip(const uint8_t* src, size_t srclen, uint8_t* dst, size_t
 }
 
 int main(int argc, char** argv) {
-  if (argc != 3) {
-    fprintf(stderr, "usage: %s buffers.bin members.bin\n", argv[0]);
+  if (argc != 3 && argc != 4) {
+    fprintf(stderr, "usage: %s buffers.bin members.bin [dynamic]\n", argv[0]);
     return 2;
   }
+  const int32_t dynamic = argc == 4 ? (int32_t)atoi(argv[3]) : 0;
   FILE* f = fopen(argv[1], "rb");
   FILE* g = fopen(argv[2], "wb");
   if (!f || !g) {
@@ -83,7 +85,9 @@ int main(int argc, char** argv) {
     if (fread(hb, 1, 8, f) != 8) break;
     const size_t len = rd32le(hb);
     zh_gzip_enc_params prm;
+    memset(&prm, 0, sizeof prm);
     prm.blocksize = (int32_t)rd32le(hb + 4);
+    prm.dynamic = dynamic;
     // exact-size heap copies: the sanitizer sees any access past either end
     uint8_t* buf = (uint8_t*)malloc(len ? len : 1);
     if (len && fread(buf, 1, len, f) != len) {

@@ -122,7 +122,7 @@ class zh_zstd_enc_frame(C.Structure):
 
 class zh_gzip_enc_params(C.Structure):
     """How gzip members are written (zarrhip.h zh_gzip_enc_params)."""
-    _fields_ = [("blocksize", C.c_int32)]
+    _fields_ = [("blocksize", C.c_int32), ("dynamic", C.c_int32)]
 
 
 class zh_gzip_enc_frame(C.Structure):

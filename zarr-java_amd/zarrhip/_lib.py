@@ -125,6 +125,8 @@ _SIGS = {
     "zh_debug_gzip_encode_kernel_ms": (C.c_double, []),
     "zh_debug_gzip_encode_kernel_parts_ms": (None, [C.POINTER(C.c_double)]),
     "zh_debug_gzip_crc32": (C.c_int, [P, C.POINTER(A.zh_gzip_enc_frame), I64, C.POINTER(U32)]),
+    "zh_debug_gzip_code_lengths": (C.c_int, [P, C.POINTER(U32), C.c_int32, C.c_int32, I64,
+                                             C.POINTER(C.c_uint8)]),
     "zh_zstd_batch_plan": (I64, [C.POINTER(A.zh_zstd_frame), I64, CH, SZ]),
     "zh_zstd_decode_batch": (C.c_int, [P, C.POINTER(A.zh_zstd_frame), I64, P, I64, P, CH, SZ]),
     "zh_debug_zstd_decode_kernel_ms": (C.c_double, []),
@@ -603,28 +605,30 @@ class DeviceContext:
         check(self.L.zh_debug_zstd_xxh64(self.h, arr, n, out))
         return [int(out[i]) for i in range(n)]
 
-    def gzip_encode_batch_raw(self, sources, blocksize=0, stream=None, take=None):
+    def gzip_encode_batch_raw(self, sources, blocksize=0, stream=None, take=None, dynamic=False):
         """zh_gzip_encode_bound + zh_gzip_encode_batch over (device address, nbytes) pairs:
         (the host buffer the members arrived in, [(dst_off, cbytes)] per source).  `take(n)`: a
-        uint8 array of n bytes to receive them (default: a fresh one)."""
+        uint8 array of n bytes to receive them (default: a fresh one).  `dynamic`:
+        dynamic-Huffman segments join the per-block choice."""
         import numpy as np
         n = len(sources)
         arr = (A.zh_gzip_enc_frame * max(1, n))()
         for i, (addr, nb) in enumerate(sources):
             arr[i].src, arr[i].nbytes = addr, int(nb)
-        prm = A.zh_gzip_enc_params(int(blocksize))
+        prm = A.zh_gzip_enc_params(int(blocksize), int(dynamic))
         bound = self.L.zh_gzip_encode_bound(arr, n, C.byref(prm))
         if bound < 0:
-            raise ZhError(int(-bound), "gzip encode: blocksize >= 0, sizes >= 0")
+            raise ZhError(int(-bound), "gzip encode: blocksize >= 0, sizes >= 0"
+                          if int(dynamic) in (0, 1) else "gzip encode: dynamic is 0 or 1")
         out = (take or (lambda k: np.empty(k, np.uint8)))(max(1, bound))
         err = C.create_string_buffer(1024)
         check(self.L.zh_gzip_encode_batch(self.h, arr, n, C.byref(prm), P(out.ctypes.data),
                                           bound, P(stream), err, 1024), err)
         return out, [(int(arr[i].dst_off), int(arr[i].cbytes)) for i in range(n)]
 
-    def gzip_encode_batch(self, sources, blocksize=0, stream=None, take=None):
+    def gzip_encode_batch(self, sources, blocksize=0, stream=None, take=None, dynamic=False):
         """The gzip members of (device address, nbytes) sources as a list of bytes."""
-        out, rows = self.gzip_encode_batch_raw(sources, blocksize, stream, take)
+        out, rows = self.gzip_encode_batch_raw(sources, blocksize, stream, take, dynamic)
         mv = memoryview(out)
         return [bytes(mv[o:o + n]) for o, n in rows]
 
@@ -638,6 +642,10 @@ class DeviceContext:
         out = (U32 * max(1, n))()
         check(self.L.zh_debug_gzip_crc32(self.h, arr, n, out))
         return [int(out[i]) for i in range(n)]
+
+    def gzip_code_lengths(self, rows, limit):
+        """zh_debug_gzip_code_lengths on the device: see gzip_code_lengths."""
+        return gzip_code_lengths(rows, limit, self.h)
 
     def host_staging(self, nbytes):
         """zh_host_staging: the context's page-locked staging (valid until the next call)."""
@@ -837,12 +845,13 @@ def zstd_compress(data, checksum=True, blocksize=0):
     return bytes(out[:n.value])
 
 
-def gzip_compress(data, blocksize=0):
+def gzip_compress(data, blocksize=0, dynamic=False):
     """zh_gzip_compress (no device): one gzip member of `data`, its content cut into blocks of
-    `blocksize` bytes (0: the default) that are compressed on their own."""
+    `blocksize` bytes (0: the default) that are compressed on their own; `dynamic`:
+    dynamic-Huffman segments join the per-block choice."""
     L = lib()
     data = bytes(data)
-    prm = A.zh_gzip_enc_params(int(blocksize))
+    prm = A.zh_gzip_enc_params(int(blocksize), int(dynamic))
     n = SZ()
     err = C.create_string_buffer(256)
     check(L.zh_gzip_compress(data, len(data), C.byref(prm), None, 0, C.byref(n), err, 256), err)
@@ -850,6 +859,21 @@ def gzip_compress(data, blocksize=0):
     check(L.zh_gzip_compress(data, len(data), C.byref(prm), out, n.value, C.byref(n), err, 256),
           err)
     return bytes(out[:n.value])
+
+
+def gzip_code_lengths(rows, limit, ctx=None):
+    """zh_debug_gzip_code_lengths: the code lengths (at most `limit` bits) the gzip writer's
+    dynamic form gives each histogram of `rows` (equally long lists of counts), as lists; on the
+    host, or with a context handle one wavefront per histogram on the device."""
+    rows = [list(r) for r in rows]
+    if not rows:
+        return []
+    nsym = len(rows[0])
+    assert all(len(r) == nsym for r in rows)
+    counts = (U32 * (len(rows) * nsym))(*[c for r in rows for c in r])
+    lens = (C.c_uint8 * (len(rows) * nsym))()
+    check(lib().zh_debug_gzip_code_lengths(ctx, counts, nsym, int(limit), len(rows), lens))
+    return [list(lens[k * nsym:(k + 1) * nsym]) for k in range(len(rows))]
 
 
 def gzip_frame_array(frames):

@@ -14,8 +14,8 @@ and gzip members, which one batched call decodes on the device when the codec is
 host stage (ZH_BLOSC_DEVICE, zh_blosc_decode_batch; ZH_ZSTD_DEVICE, zh_zstd_decode_batch;
 ZH_GZIP_DEVICE, zh_gzip_decode_batch), and blosc LZ4 and zstd frames, which Array.write
 compresses on the device (ZH_BLOSC_ENCODE_DEVICE, zh_blosc_encode_batch; ZH_ZSTD_ENCODE_DEVICE,
-zh_zstd_encode_batch), as it does gzip members when asked to (ZH_GZIP_ENCODE_DEVICE=1,
-zh_gzip_encode_batch).
+zh_zstd_encode_batch), as it does gzip members when asked to (ZH_GZIP_ENCODE_DEVICE=1, or 2
+for dynamic-Huffman segments as well; zh_gzip_encode_batch).
 """
 import atexit
 import ctypes as C
@@ -66,10 +66,12 @@ BLOSC_ENCODE_DEVICE_DEFAULT = "1"
 # ZH_ZSTD_ENCODE_DEVICE: the same for a zstd chain (zh_zstd_encode_batch), and "1" for the same
 # reason (DESIGN.md "Zstd frames encoded on the device").
 ZSTD_ENCODE_DEVICE_DEFAULT = "1"
-# ZH_GZIP_ENCODE_DEVICE: "1" sends a gzip chain's members to the device (zh_gzip_encode_batch).
-# The default is "0": the device writer has no dynamic-Huffman blocks, so bytes that LZ alone does
-# not shrink are stored where zlib would still compress them (DESIGN.md "Gzip members encoded on
-# the device"); with the switch unset every stored byte is zlib's.
+# ZH_GZIP_ENCODE_DEVICE: "1" sends a gzip chain's members to the device (zh_gzip_encode_batch)
+# with stored and fixed-Huffman segments only, so bytes that LZ alone does not shrink are stored
+# where zlib would still compress them; "2" does the same with dynamic-Huffman segments in the
+# per-block choice (zh_gzip_enc_params::dynamic = 1).  The default is "0" (DESIGN.md "Gzip
+# members encoded on the device" and "Dynamic-Huffman segments"): with the switch unset every
+# stored byte is zlib's.
 GZIP_ENCODE_DEVICE_DEFAULT = "0"
 
 
@@ -944,7 +946,8 @@ class Array:
         (zh_blosc_encode_batch / zh_zstd_encode_batch / zh_gzip_encode_batch), else None: the
         codec is the only host byte-to-byte stage, one device is in use and the codec's switch
         (ZH_BLOSC_ENCODE_DEVICE / ZH_ZSTD_ENCODE_DEVICE) is not "0", or, for gzip, whose host
-        route is zlib and stores other bytes, ZH_GZIP_ENCODE_DEVICE is "1".  Blosc: its cname is
+        route is zlib and stores other bytes, ZH_GZIP_ENCODE_DEVICE is "1" or "2" ("2": with
+        dynamic-Huffman segments, _gzip_dynamic).  Blosc: its cname is
         lz4 / lz4hc (the one blosc compressor written here; clevel is not honoured, as the level
         of zstd and gzip is not)."""
         if len(devices()) != 1:
@@ -957,9 +960,14 @@ class Array:
             on = os.environ.get("ZH_ZSTD_ENCODE_DEVICE", ZSTD_ENCODE_DEVICE_DEFAULT) != "0"
             return "zstd" if on else None
         if self._gzip_chain():
-            on = os.environ.get("ZH_GZIP_ENCODE_DEVICE", GZIP_ENCODE_DEVICE_DEFAULT) == "1"
+            on = os.environ.get("ZH_GZIP_ENCODE_DEVICE", GZIP_ENCODE_DEVICE_DEFAULT) in ("1", "2")
             return "gzip" if on else None
         return None
+
+    @staticmethod
+    def _gzip_dynamic():
+        """The device's gzip members may hold dynamic-Huffman segments."""
+        return os.environ.get("ZH_GZIP_ENCODE_DEVICE", GZIP_ENCODE_DEVICE_DEFAULT) == "2"
 
     def _frames_device(self, dev, bufs, sizes, info, kind):
         """The stored objects of the chunks with sz > 0, their frames (`kind`: blosc, zstd, gzip)
@@ -978,8 +986,10 @@ class Array:
             def batch(sources, take):
                 return dev.zstd_encode_batch(sources, bool(codec.checksum), take=take)
         else:
+            dynamic = self._gzip_dynamic()
+
             def batch(sources, take):
-                return dev.gzip_encode_batch(sources, take=take)
+                return dev.gzip_encode_batch(sources, take=take, dynamic=dynamic)
         sources, shards = [], {}
         if sharded:
             n_in = self._n_inner()

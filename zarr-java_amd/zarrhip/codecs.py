@@ -239,9 +239,10 @@ class Crc32cCodec(Codec):
 class GzipCodec(Codec):
     """GzipCodec (M/v3/codec/core/GzipCodec.java:35-46) — host only: zlib both ways.
     Array.write makes a gzip chain's members on the device instead when ZH_GZIP_ENCODE_DEVICE
-    is 1 (zh_gzip_encode_batch: other bytes than zlib's, `level` not honoured); decode reads
-    both.  Array.read decodes a gzip chain's members on the device instead when ZH_GZIP_DEVICE
-    says so (zh_gzip_decode_batch, the library's own DEFLATE reader; a corrupt member is then
+    is 1 (zh_gzip_encode_batch: stored and fixed-Huffman segments, other bytes than zlib's,
+    `level` not honoured) or 2 (the same with dynamic-Huffman segments where they are smaller);
+    decode reads all of them.  Array.read decodes a gzip chain's members on the device instead
+    when ZH_GZIP_DEVICE says so (zh_gzip_decode_batch, the library's own DEFLATE reader; a corrupt member is then
     ZarrException("Error in decoding gzip."), the reference's).  decode() here stays zlib and a
     corrupt member raises the bare zlib.error: moving it to zh_gzip_decompress is a follow-up."""
     name, kind = "gzip", "bb"
