@@ -630,6 +630,26 @@ double zh_debug_blosc_kernel_ms(void);
 int64_t zh_debug_blosc_streams(const void* src, size_t srclen, int64_t* rows, int64_t cap,
                                char* err, size_t errlen);
 
+/* The three calls above with flags; flags = 0 is exactly those calls, any unknown bit is
+ * ZH_EINVAL.  ZH_BLOSC_ZSTD_DEVICE: a frame with compressor code 4 (zstd) is planned where = 0
+ * when its block / stream chain is sound and every stream is stored raw or ONE zstd frame that
+ * ends at the stream's last byte, has no dictionary and no checksum, and whose content size is
+ * the stream's raw size (what ZSTD_compress, which c-blosc calls, writes).  Such streams are
+ * decoded one wavefront each by the library's zstd frame decoder into the block's window before
+ * the kernel above undoes the shuffle; the diagnostic reports them with method 3.  Any other
+ * zstd frame (a stream with a checksum, without or with another content size, concatenated or
+ * skippable frames) stays where = 1.  zlib payloads stay on the host.  The device memory of one
+ * launch is bounded: at most 128 MiB of decoded zstd frames go into one slab (a larger frame is
+ * its own), and a slab's literal scratch and shuffle temporary are each at most its decoded
+ * bytes.  zh_debug_blosc_kernel_ms covers both kernels of every slab. */
+#define ZH_BLOSC_ZSTD_DEVICE 1u
+int64_t zh_blosc_batch_plan_ex(zh_blosc_frame* frames, int64_t n, unsigned flags, char* err,
+                               size_t errlen);
+int zh_blosc_decode_batch_ex(zh_ctx* ctx, zh_blosc_frame* frames, int64_t n, unsigned flags,
+                             void* dst, int64_t dstcap, void* stream, char* err, size_t errlen);
+int64_t zh_debug_blosc_streams_ex(const void* src, size_t srclen, unsigned flags, int64_t* rows,
+                                  int64_t cap, char* err, size_t errlen);
+
 /* ---- blosc1 LZ4 frames written on the host and on the device ---------------------------
  * The writer of the frames the decoders above read: version 2, compressor code 1 (LZ4), byte
  * or bit shuffle (format-2 rule), blocks of at most 64 KiB (a larger configured block size is

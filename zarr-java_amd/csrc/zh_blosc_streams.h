@@ -20,12 +20,17 @@
 //   * unshuffle_byte_at: where output byte q of a block comes from in the shuffled block.
 //   * decode_frame_serial: the whole frame on the host with SerialCopy (the sanitizer checker
 //     tools/blosc_stream_check.cpp; the table and parsers the kernel runs, without a device).
+//   * zstd streams (compressor code 4) enter the table only when the caller passes
+//     ZH_BLOSC_ZSTD_DEVICE: a stream is then stored raw or ONE plain zstd frame (zstd_stream_ok),
+//     method kZstd, decoded by zh_zstd_dec.h's decode_frame and not by decode_stream.  Without
+//     the flag, or with any other kind of stream, the frame is the host decoder's.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/zarrhip.h"
+#include "zh_zstd_dec.h"
 
 #if defined(__HIPCC__)
 #define ZH_BS_HD __host__ __device__ inline
@@ -35,7 +40,7 @@
 
 namespace zh_bs {
 
-enum Method : uint32_t { kRaw = 0, kLz4 = 1, kBloscLz = 2 };
+enum Method : uint32_t { kRaw = 0, kLz4 = 1, kBloscLz = 2, kZstd = 3 };
 // kShufBit2: c-blosc 1.x (frame version <= 2) bit-shuffles a block only when its element count
 // is a multiple of 8; kShufBit3: later formats shuffle the multiple-of-8 prefix.
 enum Shuffle : uint32_t { kShufNone = 0, kShufByte = 1, kShufBit2 = 2, kShufBit3 = 3 };
@@ -47,6 +52,7 @@ struct BlockRow {
 struct StreamRow {
   int64_t src_off;  // offset of the payload in the frame
   uint32_t csize, blk_off, rawsize, method;
+  uint32_t max_regen;  // kZstd: the largest Huffman literals section (its literal scratch)
 };
 
 struct SerialCopy {
@@ -238,19 +244,33 @@ inline int parse_header(const uint8_t* src, size_t srclen, Header* h, const char
 }
 
 // Where a frame is decoded: 0 device streams, 1 host (zlib / zstd payloads), 2 memcpyed.
+// (With ZH_BLOSC_ZSTD_DEVICE a zstd frame whose table build_table accepts is 0: the plan's.)
 inline int frame_where(const Header& h) {
   if (h.memcpyed) return 2;
   return (h.comp == 3 || h.comp == 4) ? 1 : 0;
 }
 
+// What the device route takes of a zstd stream of `neb` raw bytes: one frame that ends exactly
+// at the stream's last byte, no dictionary, no checksum, and a content size that is the stream's
+// raw size (what ZSTD_compress, which c-blosc calls, writes).  Concatenated and skippable
+// frames, a checksum, a missing or different content size: the host decoder's.
+inline bool zstd_stream_ok(const uint8_t* s, size_t n, size_t neb, uint32_t* max_regen) {
+  const zh_zd::Walk w = zh_zd::walk_frame<zh_zd::NoRows>(s, n, nullptr);
+  if (!w.device || w.csum || w.fcs != (int64_t)neb) return false;
+  *max_regen = (uint32_t)w.max_regen;  // <= fcs == neb < 2^32
+  return true;
+}
+
 // Block and stream rows of a frame whose header parse_header accepted and that is neither
-// memcpyed nor host-decoded.  V: a vector-like with push_back / size.  Walks the frame as
-// zh_blosc_decompress does; at the first field that fails returns that decoder's status and
+// memcpyed nor host-decoded.  `flags`: ZH_BLOSC_ZSTD_DEVICE admits compressor code 4; a stream
+// zstd_stream_ok refuses makes the frame host-decoded (ZH_EUNSUPPORTED, as without the flag).
+// V: a vector-like with push_back / size.  Walks the frame as zh_blosc_decompress does; at the first field that fails returns that decoder's status and
 // text with the rows of the blocks before it in place (the failing block's rows are dropped).
 template <class VB, class VS>
 inline int build_table(const uint8_t* src, size_t srclen, const Header& h, VB& blocks,
-                       VS& streams, const char** msg) {
-  if (h.comp != 0 && h.comp != 1) {
+                       VS& streams, const char** msg, unsigned flags = 0) {
+  const bool zstd = h.comp == 4 && (flags & ZH_BLOSC_ZSTD_DEVICE);
+  if (h.comp != 0 && h.comp != 1 && !zstd) {
     *msg = h.comp == 2 ? "blosc compressor (snappy) not available on this host"
                        : "blosc payload is decoded on the host";
     return ZH_EUNSUPPORTED;
@@ -292,7 +312,12 @@ inline int build_table(const uint8_t* src, size_t srclen, const Header& h, VB& b
       r.csize = (uint32_t)cs;
       r.blk_off = (uint32_t)(sidx * neb);
       r.rawsize = (uint32_t)neb;
-      r.method = cs == neb ? kRaw : (h.comp == 0 ? kBloscLz : kLz4);
+      r.method = cs == neb ? kRaw : zstd ? kZstd : (h.comp == 0 ? kBloscLz : kLz4);
+      r.max_regen = 0;
+      if (r.method == kZstd && !zstd_stream_ok(src + p, cs, neb, &r.max_regen)) {
+        *msg = "blosc payload is decoded on the host";
+        return ZH_EUNSUPPORTED;
+      }
       p += cs;
     }
     for (size_t sidx = 0; sidx < nsplit; sidx++) streams.push_back(rows[sidx]);

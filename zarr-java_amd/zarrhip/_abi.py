@@ -24,6 +24,8 @@ ZH_MALLOC_SCATTER = 0x4
 ZH_MALLOC_CALIBRATE = 0x8
 ZH_MALLOC_PLAIN = 0x10
 ZH_OUT_DEVICE = 0x2
+# zh_blosc_batch_plan_ex / zh_blosc_decode_batch_ex / zh_debug_blosc_streams_ex flags
+ZH_BLOSC_ZSTD_DEVICE = 0x1
 # zh_array_read_multi_routed per-slab routes (include/zarrhip.h)
 ZH_ROUTE_DIRECT = 0
 ZH_ROUTE_PEER = 1

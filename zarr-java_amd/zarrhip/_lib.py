@@ -97,6 +97,10 @@ _SIGS = {
     "zh_blosc_decode_batch": (C.c_int, [P, C.POINTER(A.zh_blosc_frame), I64, P, I64, P, CH, SZ]),
     "zh_debug_blosc_kernel_ms": (C.c_double, []),
     "zh_debug_blosc_streams": (I64, [P, SZ, PI64, I64, CH, SZ]),
+    "zh_blosc_batch_plan_ex": (I64, [C.POINTER(A.zh_blosc_frame), I64, C.c_uint, CH, SZ]),
+    "zh_blosc_decode_batch_ex": (C.c_int, [P, C.POINTER(A.zh_blosc_frame), I64, C.c_uint, P, I64,
+                                           P, CH, SZ]),
+    "zh_debug_blosc_streams_ex": (I64, [P, SZ, C.c_uint, PI64, I64, CH, SZ]),
     "zh_blosc_compress": (C.c_int, [P, SZ, C.POINTER(A.zh_blosc_enc_params), P, SZ,
                                     C.POINTER(SZ), CH, SZ]),
     "zh_blosc_encode_bound": (I64, [C.POINTER(A.zh_blosc_enc_frame), I64,
@@ -452,20 +456,21 @@ class DeviceContext:
         check(st, err)
         return [int(sizes[i]) for i in range(n)]
 
-    def blosc_decode_batch(self, frames, stream=None):
-        """zh_blosc_batch_plan + zh_blosc_decode_batch over blosc1 frames (bytes-like, or
+    def blosc_decode_batch(self, frames, stream=None, flags=0):
+        """zh_blosc_batch_plan_ex + zh_blosc_decode_batch_ex over blosc1 frames (bytes-like, or
         (address, nbytes) pairs of host memory the caller keeps alive): returns the device
         buffer holding every decoded frame and, per frame, (dst_off, nbytes, where).  The
-        caller frees the buffer (self.free)."""
+        caller frees the buffer (self.free).  flags: 0, or A.ZH_BLOSC_ZSTD_DEVICE (frames whose
+        streams are plain zstd frames are decoded on the device too)."""
         arr, keep = blosc_frame_array(frames)
         err = C.create_string_buffer(1024)
-        total = self.L.zh_blosc_batch_plan(arr, len(frames), err, 1024)
+        total = self.L.zh_blosc_batch_plan_ex(arr, len(frames), int(flags), err, 1024)
         if total < 0:
             check(int(-total), err)
         ptr = self.malloc(max(256, total), A.ZH_MALLOC_PLAIN)
         try:
-            check(self.L.zh_blosc_decode_batch(self.h, arr, len(frames), P(ptr), max(256, total),
-                                               P(stream), err, 1024), err)
+            check(self.L.zh_blosc_decode_batch_ex(self.h, arr, len(frames), int(flags), P(ptr),
+                                                  max(256, total), P(stream), err, 1024), err)
         except BaseException:
             self.free(ptr)
             raise
@@ -819,11 +824,11 @@ def zstd_blocks(frame):
     return [tuple(rows[10 * k:10 * k + 10]) for k in range(n)]
 
 
-def blosc_batch_plan(frames):
-    """zh_blosc_batch_plan (no device): (destination bytes, [(dst_off, nbytes, where)])."""
+def blosc_batch_plan(frames, flags=0):
+    """zh_blosc_batch_plan_ex (no device): (destination bytes, [(dst_off, nbytes, where)])."""
     arr, keep = blosc_frame_array(frames)
     err = C.create_string_buffer(1024)
-    total = lib().zh_blosc_batch_plan(arr, len(frames), err, 1024)
+    total = lib().zh_blosc_batch_plan_ex(arr, len(frames), int(flags), err, 1024)
     if total < 0:
         check(int(-total), err)
     return int(total), [(arr[i].dst_off, arr[i].nbytes, arr[i].where)
@@ -967,16 +972,17 @@ def blosc_compress(data, typesize, shuffle, blocksize=0):
     return out.raw[:n.value]
 
 
-def blosc_streams(frame):
-    """zh_debug_blosc_streams (no device): the block / stream rows of one frame, 6 ints each."""
+def blosc_streams(frame, flags=0):
+    """zh_debug_blosc_streams_ex (no device): the block / stream rows of one frame, 6 ints
+    each."""
     L = lib()
     b = (C.c_char * max(1, len(frame))).from_buffer_copy(bytes(frame) or b"\0")
     err = C.create_string_buffer(1024)
-    n = L.zh_debug_blosc_streams(b, len(frame), None, 0, err, 1024)
+    n = L.zh_debug_blosc_streams_ex(b, len(frame), int(flags), None, 0, err, 1024)
     if n < 0:
         check(int(-n), err)
     rows = (C.c_int64 * max(1, 6 * n))()
-    L.zh_debug_blosc_streams(b, len(frame), rows, n, err, 1024)
+    L.zh_debug_blosc_streams_ex(b, len(frame), int(flags), rows, n, err, 1024)
     return [tuple(rows[6 * k:6 * k + 6]) for k in range(n)]
 
 

@@ -40,6 +40,12 @@ _ctx_lock = threading.Lock()
 # device in one batch (zh_blosc_decode_batch) instead of decoding them here one at a time.
 # The default follows the measurement in DESIGN.md ("Blosc frames on the device").
 BLOSC_DEVICE_DEFAULT = "1"
+# ZH_BLOSC_ZSTD_DEVICE: on that route, "1" passes ZH_BLOSC_ZSTD_DEVICE to the batch, so frames
+# whose streams are plain zstd frames (c-blosc's, and the codec's default cname) are decoded on
+# the device as well; "0" passes no flag and such frames are decoded by zh_blosc_decompress inside
+# the batch call, as before.  The default follows the measurement in DESIGN.md ("Blosc zstd
+# streams on the device").
+BLOSC_ZSTD_DEVICE_DEFAULT = "0"
 # ZH_ZSTD_DEVICE: the same for chains whose only host byte-to-byte stage is zstd
 # (zh_zstd_decode_batch).  "0": the host route; "2": every eligible read goes to the device;
 # "1" (the default): the rule of DESIGN.md ("Zstd frames on the device"), a read goes to the
@@ -558,7 +564,8 @@ class Array:
             return
         if self._blosc_device(devs):
             self._read_frames_device(coords, offset, shape, out_addr, flags, devs[0], parallel,
-                                     t_enter, t0, devs[0].blosc_decode_batch, _raise_blosc, "blosc")
+                                     t_enter, t0, self._blosc_decode_batch(devs[0]), _raise_blosc,
+                                     "blosc")
             return
         if self._zstd_device(devs, coords):
             self._read_frames_device(coords, offset, shape, out_addr, flags, devs[0], parallel,
@@ -647,6 +654,13 @@ class Array:
     def _blosc_device(self, devs):
         return (len(devs) == 1 and self._blosc_chain() and
                 os.environ.get("ZH_BLOSC_DEVICE", BLOSC_DEVICE_DEFAULT) != "0")
+
+    @staticmethod
+    def _blosc_decode_batch(dev):
+        """DeviceContext.blosc_decode_batch with the flags of ZH_BLOSC_ZSTD_DEVICE."""
+        on = os.environ.get("ZH_BLOSC_ZSTD_DEVICE", BLOSC_ZSTD_DEVICE_DEFAULT) != "0"
+        flags = A.ZH_BLOSC_ZSTD_DEVICE if on else 0
+        return lambda frames: dev.blosc_decode_batch(frames, flags=flags)
 
     def _zstd_chain(self):
         """The chain's host byte-to-byte stages are exactly one ZstdCodec."""

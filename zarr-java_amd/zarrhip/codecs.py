@@ -269,7 +269,10 @@ class GzipCodec(Codec):
 class BloscCodec(Codec):
     """BloscCodec (M/v3/codec/core/BloscCodec.java) — host only.  Frames are decoded by
     zh_blosc_decompress (BloscLZ / LZ4 / zlib / zstd payloads, byte and bit shuffle; snappy
-    raises UnsupportedChainError).  encode compresses cname lz4 / lz4hc with the library's own
+    raises UnsupportedChainError).  Array.read hands the frames of a chain whose only host stage
+    is this codec to the device in one batch instead (ZH_BLOSC_DEVICE: LZ4 / BloscLZ / raw
+    streams; with ZH_BLOSC_ZSTD_DEVICE=1 also frames whose streams are plain zstd frames, the
+    default cname's; zlib payloads stay with zh_blosc_decompress).  encode compresses cname lz4 / lz4hc with the library's own
     LZ4 writer (zh_blosc_compress: byte-identical to the frames Array.write makes on the
     device; clevel is not honoured, and blocks are at most 64 KiB); every other cname is
     written as a MEMCPYED frame (no compressor for it here)."""
