@@ -176,9 +176,11 @@ int zh_blosc_decompress(const void* src_v, size_t srclen, void* dst_v, size_t ds
   }
   size_t nblocks = 0;
   if (!memcpyed && nbytes > 0) {
-    // no codec here expands a stream by more than ~1032x (deflate), so a larger nbytes is a
-    // corrupt header
-    if (bsize == 0 || ts == 0 || nbytes > 2048 * (size_t)cbytes + 65536) {
+    // DEFLATE expands a stream 1032 times at the most and the LZ codecs less; a zstd RLE block
+    // is 128 KiB from 4 bytes (32768 times: ZstdCodec.decode's bound).  A larger nbytes is a
+    // corrupt header.
+    const size_t expand = (flags >> 5) == 4 ? 32768 : 2048;
+    if (bsize == 0 || ts == 0 || nbytes > expand * (size_t)cbytes + 65536) {
       set_err(err, errlen, "corrupt blosc header");
       return ZH_EDATA;
     }

@@ -229,8 +229,9 @@ inline int parse_header(const uint8_t* src, size_t srclen, Header* h, const char
     return ZH_EDATA;
   }
   if (!h->memcpyed && h->nbytes > 0) {
+    const size_t expand = h->comp == 4 ? 32768 : 2048;  // zstd: an RLE block (zh_blosc.cpp)
     if (h->blocksize == 0 || h->typesize == 0 ||
-        h->nbytes > 2048 * (size_t)h->cbytes + 65536) {
+        h->nbytes > expand * (size_t)h->cbytes + 65536) {
       *msg = "corrupt blosc header";
       return ZH_EDATA;
     }
