@@ -692,9 +692,31 @@ int zh_blosc_encode_batch(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
                           const zh_blosc_enc_params* params, void* dst, int64_t dstcap,
                           void* stream, char* err, size_t errlen);
 
-/* Diagnostic: milliseconds the two kernels of the last successful zh_blosc_encode_batch took,
- * by device events around their launches, summed over its slabs (-1: none yet). */
+/* Diagnostic: milliseconds the kernels of the last successful zh_blosc_encode_batch or
+ * zh_blosc_encode_batch_ex took, by device events around their launches, summed over its slabs
+ * (-1: none yet). */
 double zh_debug_blosc_encode_kernel_ms(void);
+
+/* The same writer with flags.  flags = 0: exactly the two calls above.  ZH_BLOSC_ENC_ZSTD: the
+ * frame carries compressor code 4 and its streams are zstd frames: same block size rule,
+ * shuffle flags, split rule and block starts; a stream's payload is, byte for byte, what
+ * zh_zstd_compress writes for the stream's shuffled bytes with checksum 0 and blocksize 64 KiB
+ * (one frame of one compressed block behind the 13-byte header with the 8-byte content size)
+ * when that is shorter than the stream, else the raw bytes.  A frame that would pass
+ * nbytes + 16 is written MEMCPYED; zh_blosc_encode_bound holds for every flag.  The batch call
+ * runs three kernels per slab (match finder: one workgroup per block, one wavefront per
+ * stream; sequence coder: one thread per stream; raw streams) before the layout kernel; a slab's
+ * device memory is its raw bytes three and a half times over (scratch: the raw size and 16
+ * bytes per stream; records: 1.5 x; the compact frames) and the small tables.  Any other bit →
+ * ZH_EINVAL.  zh_blosc_decompress, libzstd on the streams, and zh_blosc_decode_batch_ex with
+ * ZH_BLOSC_ZSTD_DEVICE read these frames. */
+#define ZH_BLOSC_ENC_ZSTD 1u
+int zh_blosc_compress_ex(const void* src, size_t n, const zh_blosc_enc_params* params,
+                         unsigned flags, void* dst, size_t cap, size_t* cbytes, char* err,
+                         size_t errlen);
+int zh_blosc_encode_batch_ex(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
+                             const zh_blosc_enc_params* params, unsigned flags, void* dst,
+                             int64_t dstcap, void* stream, char* err, size_t errlen);
 
 /* ---- host byte-to-byte stage: zstd frames (RFC 8878) ------------------------------
  * Replaces zstd-jni inside ZstdCodec.decode (M/core/codec/core/ZstdCodec.java:14-22) and the

@@ -1,9 +1,11 @@
-// zh_blosc_enc.h — the blosc1 LZ4 frame writer shared by the host and the device.
+// zh_blosc_enc.h — the blosc1 frame writer shared by the host and the device: LZ4 streams, or
+// (ZH_BLOSC_ENC_ZSTD) zstd streams.
 //
 // The writer emits what zh_blosc_streams.h reads (build_table is the contract): version 2,
-// versionlz 1, compressor code 1 (LZ4), flags 0x01 byte shuffle / 0x04 bit shuffle (format-2
-// rule: kShufBit2) / 0x10 blocks not split, the block starts, then per stream an int32 csize and
-// the payload.  This header holds what both sides need, and nothing that needs a device:
+// versionlz 1, compressor code 1 (LZ4) or 4 (zstd: with_compressor), flags 0x01 byte shuffle /
+// 0x04 bit shuffle (format-2 rule: kShufBit2) / 0x10 blocks not split, the block starts, then per
+// stream an int32 csize and the payload.  This header holds what both sides need, and nothing
+// that needs a device:
 //   * make_layout: block size, split rule and flags of a frame of n bytes;
 //   * shuffled_byte_at: byte o of the shuffled block, read from the raw block (the inverse of
 //     zh_bs::unshuffle_byte_at);
@@ -12,8 +14,15 @@
 //     (HostLanes there, the kernel's WaveLanes in zh_enc_device.h), so the output is a pure
 //     function of (input bytes, n).  A stream whose encoding would reach its raw size returns
 //     n before writing past out[n - 1]: the caller stores it raw;
-//   * compress_frame: the whole frame on the host with HostLanes (zh_blosc_compress, the
-//     kernel's byte-for-byte oracle, tools/blosc_enc_check.cpp under sanitizers).
+//   * compress_frame: the whole frame on the host with HostLanes (zh_blosc_compress[_ex], the
+//     kernels' byte-for-byte oracle, tools/blosc_enc_check.cpp and blosc_zstd_enc_check.cpp
+//     under sanitizers) over a stream coder: Lz4Coder (encode_stream) or ZstdCoder.
+// Zstd streams (compressor code 4): the layout, the shuffles and the split rule are the LZ4
+// writer's.  A stream's payload is, byte for byte, the frame zh_zstd_compress writes for the
+// shuffled bytes with checksum 0 and block size 64 KiB: the 13-byte header with the 8-byte
+// content size, then one compressed block under its 3-byte header (a stream is at most 64 KiB:
+// always one block), zh_ze::match_block and zh_ze::fse_block behind kZstdHead bytes.  A stream
+// whose kZstdHead + block size would reach its raw size is stored raw (zstd_stream_size).
 // LZ4 end rules (liblz4 decodes the streams): the last 5 bytes are literals, no match starts
 // within the last 12 bytes, a stream shorter than 13 bytes is never encoded, offsets are
 // 1..65535 (a stream is at most 64 KiB).
@@ -24,6 +33,7 @@
 
 #include "zh_blosc_streams.h"
 #include "zh_lz_match.h"
+#include "zh_zstd_enc.h"
 
 namespace zh_be {
 
@@ -61,6 +71,11 @@ inline int make_layout(size_t n, const zh_blosc_enc_params* p, Layout* L) {
   L->flags = (1u << 5) | (p->shuffle == 1 ? 0x01u : 0u) | (p->shuffle == 2 ? 0x04u : 0u) |
              (L->split ? 0u : 0x10u);
   return ZH_OK;
+}
+
+// The layout with another compressor code in the flags (1 LZ4, 4 zstd).
+inline void with_compressor(Layout* L, uint32_t code) {
+  L->flags = (L->flags & 0x1Fu) | (code << 5);
 }
 
 // Size and stream count of block k (a leftover block is never split).
@@ -166,15 +181,59 @@ inline void put_header(uint8_t* d, const Layout& L, uint32_t flags, size_t n, si
 // flags of a frame written MEMCPYED (the shuffle bits stay as configured; readers ignore them)
 inline uint32_t memcpyed_flags(const Layout& L) { return (L.flags & ~0x10u) | 0x02u; }
 
+// ---- zstd streams ---------------------------------------------------------------------------
+// What stands before a stream's compressed block: the zstd frame header and the block header.
+constexpr uint32_t kZstdHead = (uint32_t)zh_ze::kFrameHeader + 3;
+// Stored size of a stream of neb raw bytes whose compressed block has cs bytes (cs >= neb: there
+// is none): neb says the stream is stored raw.
+ZH_BS_HD uint32_t zstd_stream_size(uint32_t neb, uint32_t cs) {
+  return cs < neb && kZstdHead + cs < neb ? kZstdHead + cs : neb;
+}
+
+// ---- stream coders: (stream, neb, out, table) -> stored size, neb: store the stream raw -------
+// kCode: the compressor code of the frame; kHead: room out needs beyond neb bytes.
+struct Lz4Coder {
+  static constexpr uint32_t kCode = 1, kHead = 0;
+  HostLanes w;
+  uint32_t operator()(const uint8_t* st, uint32_t neb, uint8_t* out, uint32_t* table) {
+    return encode_stream(st, neb, out, table, w);
+  }
+};
+struct ZstdCoder {
+  static constexpr uint32_t kCode = 4, kHead = kZstdHead;
+  const zh_ze::Tables& T;
+  HostLanes w;
+  uint16_t* seq;  // the records of one stream
+  explicit ZstdCoder(const zh_ze::Tables& t) : T(t), seq(new uint16_t[3 * (kMaxBlock / 4) + 3]) {
+    w.wide = true;
+  }
+  ZstdCoder(const ZstdCoder&) = delete;
+  ~ZstdCoder() { delete[] seq; }
+  uint32_t operator()(const uint8_t* st, uint32_t neb, uint8_t* out, uint32_t* table) {
+    uint8_t* blk = out + kZstdHead;
+    uint32_t nl = 0;
+    const uint32_t ns = zh_ze::match_block(st, neb, blk + 3, seq, table, w, &nl);
+    const uint32_t cs = zh_ze::fse_block(T, seq, ns, nl, blk, neb);
+    if (zstd_stream_size(neb, cs) == neb) return neb;
+    zh_ze::put_frame_header(out, neb, false);
+    const uint32_t h = zh_ze::block_header(cs, 2, true);
+    out[13] = (uint8_t)h, out[14] = (uint8_t)(h >> 8), out[15] = (uint8_t)(h >> 16);
+    return kZstdHead + cs;
+  }
+};
+
 // One frame on the host.  dst == nullptr: *cbytes = the bound n + 16.  tmp, scratch: one block
-// each (min(blocksize, n) bytes); table: kHashSize slots.
+// each (min(blocksize, n) bytes, scratch and the coder's kHead); table: kHashSize slots.
+template <class Coder>
 inline int compress_frame(const uint8_t* src, size_t n, const zh_blosc_enc_params* prm,
-                          uint8_t* dst, size_t cap, size_t* cbytes, const char** msg) {
+                          uint8_t* dst, size_t cap, size_t* cbytes, const char** msg,
+                          Coder& coder) {
   Layout L;
   if (make_layout(n, prm, &L) != ZH_OK || (n > 0 && !src)) {
     *msg = "zh_blosc_compress: typesize 1..255, shuffle 0..2, blocksize >= 0, at most 2 GiB";
     return ZH_EINVAL;
   }
+  with_compressor(&L, Coder::kCode);
   if (!dst) {
     *cbytes = n + 16;
     return ZH_OK;
@@ -187,9 +246,8 @@ inline int compress_frame(const uint8_t* src, size_t n, const zh_blosc_enc_param
   bool fits = n > 0 && pos <= n + 16;  // tiny blocks: the block starts alone can pass the bound
   if (fits) {
     uint8_t* tmp = new uint8_t[L.blocksize];
-    uint8_t* scratch = new uint8_t[L.blocksize];
+    uint8_t* scratch = new uint8_t[L.blocksize + Coder::kHead];
     uint32_t* table = new uint32_t[kHashSize];
-    HostLanes w;
     for (uint32_t k = 0; k < L.nblocks && fits; k++) {
       const uint32_t bsz = block_size(L, n, k), ns = block_streams(L, bsz), neb = bsz / ns;
       const uint8_t* in = src + (size_t)k * L.blocksize;
@@ -197,7 +255,7 @@ inline int compress_frame(const uint8_t* src, size_t n, const zh_blosc_enc_param
       wr32(dst + 16 + 4 * (size_t)k, (uint32_t)pos);
       for (uint32_t si = 0; si < ns && fits; si++) {
         const uint8_t* st = tmp + (size_t)si * neb;
-        const uint32_t cs = encode_stream(st, neb, scratch, table, w);
+        const uint32_t cs = coder(st, neb, scratch, table);
         if (pos + 4 + cs > n + 16) {
           fits = false;
           break;

@@ -1,5 +1,6 @@
-// zh_blosc_enc_kernels.hip — blosc1 LZ4 frames written on the device, a batch at a time
-// (zh_blosc_compress / zh_blosc_encode_bound / zh_blosc_encode_batch).
+// zh_blosc_enc_kernels.hip — blosc1 frames written on the device, a batch at a time, with LZ4
+// streams (zh_blosc_compress / zh_blosc_encode_bound / zh_blosc_encode_batch) or, with
+// ZH_BLOSC_ENC_ZSTD, zstd streams (zh_blosc_compress_ex / zh_blosc_encode_batch_ex).
 //
 // The raw bytes are in device memory (zh_array_write's chunk buffers); the frames go to the host.
 //   blosc_encode_kernel<CAP>   grid: one workgroup (4 waves) per block of at most CAP bytes (16,
@@ -21,7 +22,28 @@
 //           then the bytes, from scratch (streams), from the raw source (MEMCPYED frames) or from the
 //           uploaded headers and block starts, into one compact buffer of complete frames;
 //   D2H     the compact buffer through the context's page-locked out ring into host memory.
-// Slabs of at most kSlabBytes of raw input bound the scratch and the compact buffer.
+// Zstd streams (the format: zh_blosc_enc.h) take three kernels in place of the first:
+//   blosc_zstd_match_kernel<CAP>   the same grid, the same shuffled load (load_block) and the
+//           same LDS (CAP + 16 KiB of tables: 5 / 3 / 2 workgroups per CU).  After the barrier
+//           wave w runs zh_ze::match_block over WaveLanes on streams w, w+4, ...: literals to the
+//           stream's region of the scratch behind the room for the 13 + 3 + 3 header bytes, the
+//           (literal length, match length, offset) records to the stream's part of a list in
+//           global memory, the sequence and literal counts to an info table; lane 0 writes the 13
+//           bytes of the zstd frame header at the region's start.  Nothing of this is read again
+//           in this kernel;
+//   zstd_fse_kernel (zh_enc_device.h)   one thread per stream row: the sequences section behind
+//           the literals, the size of the compressed block to the size table.  The kernel
+//           boundary orders the records and literals before it;
+//   blosc_raw_stream_kernel<CAP>   one workgroup per block: where the size table says that a
+//           stream of the block is stored raw (zh_be::zstd_stream_size), the block is loaded
+//           again in its shuffled form and those streams are copied over their regions; a
+//           block without such a stream costs one read of its rows.
+// The host checks every size against its stream's raw size, lays out as above (a compressed
+// stream is two jobs: csize word + frame header, block header + block) and gathers.
+// Slabs of at most kSlabBytes of raw input bound the device memory.  LZ4: the scratch (the raw
+// size) and the compact frames (the raw size and 16 bytes per frame).  Zstd: the scratch (the
+// raw size and 16 bytes per stream), the records (6 bytes per 4 raw bytes: 1.5 x), the compact
+// frames, and per stream 36 bytes of tables.
 // Every job and block row is built on the host from validated sizes; the csize table is checked
 // against the stream sizes before it lays anything out.
 #include <hip/hip_runtime.h>
@@ -29,6 +51,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <new>
 #include <vector>
 
 #include "zh_blosc_enc.h"
@@ -135,6 +158,74 @@ __global__ __launch_bounds__(kThreads) void blosc_encode_kernel(
   }
 }
 
+// The first phase of the zstd streams: rows[b.first_stream + s] names stream s's block region
+// (out, behind the kZstdHead bytes of headers) and records (seq).
+template <uint32_t CAP>
+__global__ __launch_bounds__(kThreads) void blosc_zstd_match_kernel(
+    const EncBlock* __restrict__ blocks, const ZBlock* __restrict__ rows,
+    uint8_t* __restrict__ scratch, uint16_t* __restrict__ seqs, uint32_t* __restrict__ info) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[CAP];
+  __shared__ uint32_t tables[kWaves][zh_be::kHashSize];
+  const EncBlock b = blocks[blockIdx.x];
+  if (b.size > CAP) return;  // never: the host picks CAP from the block sizes (all threads)
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  load_block(lds, (const uint8_t*)b.src, b, threadIdx.x);
+  __syncthreads();
+  WaveLanes w;
+  w.lane = lane;
+  w.h = 0;
+  w.wide = true;
+  const uint32_t neb = b.size / b.nstreams;
+  for (uint32_t s = wave; s < b.nstreams; s += kWaves) {
+    const uint32_t k = b.first_stream + s;
+    const ZBlock r = rows[k];
+    uint32_t nl = 0;
+    const uint32_t ns = zh_ze::match_block(lds + (size_t)s * neb, neb, scratch + r.out + 3,
+                                           seqs + r.seq, tables[wave], w, &nl);
+    if (lane == 0) {
+      zh_ze::put_frame_header(scratch + r.out - zh_be::kZstdHead, neb, false);
+      info[2 * k] = ns;
+      info[2 * k + 1] = nl;
+    }
+  }
+}
+
+// The streams the size table stores raw, in their shuffled form, over their regions.
+template <uint32_t CAP>
+__global__ __launch_bounds__(kThreads) void blosc_raw_stream_kernel(
+    const EncBlock* __restrict__ blocks, const ZBlock* __restrict__ rows,
+    const uint32_t* __restrict__ csize, uint8_t* __restrict__ scratch) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[CAP];
+  const EncBlock b = blocks[blockIdx.x];
+  if (b.size > CAP) return;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t neb = b.size / b.nstreams;
+  bool any = false;  // the same for every thread: the barrier below is reached by all or none
+  for (uint32_t s = 0; s < b.nstreams; s++)
+    any |= zh_be::zstd_stream_size(neb, csize[b.first_stream + s]) == neb;
+  if (!any) return;
+  load_block(lds, (const uint8_t*)b.src, b, threadIdx.x);
+  __syncthreads();
+  for (uint32_t s = wave; s < b.nstreams; s += kWaves) {
+    const uint32_t k = b.first_stream + s;
+    if (zh_be::zstd_stream_size(neb, csize[k]) != neb) continue;
+    uint8_t* out = scratch + rows[k].out - zh_be::kZstdHead;
+    for (uint32_t q = lane; q < neb; q += 64) out[q] = lds[(size_t)s * neb + q];
+  }
+}
+
+template <uint32_t CAP>
+void launch_zstd(hipStream_t s, unsigned nblocks, unsigned nstreams, const EncBlock* blocks,
+                 const ZBlock* rows, const zh_ze::Tables* dtab, uint8_t* scratch, uint16_t* seqs,
+                 uint32_t* info, uint32_t* csize) {
+  hipLaunchKernelGGL(blosc_zstd_match_kernel<CAP>, dim3(nblocks), dim3(kThreads), 0, s, blocks,
+                     rows, scratch, seqs, info);
+  hipLaunchKernelGGL(zstd_fse_kernel, dim3((nstreams + 63) / 64), dim3(64), 0, s, rows, nstreams,
+                     dtab, scratch, (const uint16_t*)seqs, (const uint32_t*)info, csize);
+  hipLaunchKernelGGL(blosc_raw_stream_kernel<CAP>, dim3(nblocks), dim3(kThreads), 0, s, blocks,
+                     rows, (const uint32_t*)csize, scratch);
+}
+
 std::atomic<double> g_last_enc_ms{-1.0};
 
 struct FramePlan {
@@ -143,18 +234,22 @@ struct FramePlan {
   bool raw_only = false;  // the block starts alone pass the bound: MEMCPYED without a launch
 };
 
-// One slab [f0, f1) of the batch; *pos: the running offset in dst.
+// One slab [f0, f1) of the batch; *pos: the running offset in dst.  dtab: the zstd encoding
+// tables in device memory (zstd streams), or null (LZ4 streams).
 int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, zh_blosc_enc_frame* frames, int64_t f0,
-                int64_t f1, const zh_blosc_enc_params* prm, uint8_t* dst, int64_t* pos,
-                double* kernel_ms) {
+                int64_t f1, const zh_blosc_enc_params* prm, const zh_ze::Tables* dtab,
+                uint8_t* dst, int64_t* pos, double* kernel_ms) {
+  const bool zstd = dtab != nullptr;
   std::vector<FramePlan> plan((size_t)(f1 - f0));
   std::vector<EncBlock> blocks;
   std::vector<uint32_t> stream_raw;  // raw size per stream
-  int64_t scratch_total = 0, compact_cap = 0, meta_cap = 0, njobs_cap = 0;
+  std::vector<ZBlock> zrows;         // zstd: per stream, its block region and records
+  int64_t scratch_total = 0, seq_total = 0, compact_cap = 0, meta_cap = 0, njobs_cap = 0;
   for (int64_t i = f0; i < f1; i++) {
     FramePlan& fp = plan[(size_t)(i - f0)];
     const size_t n = (size_t)frames[i].nbytes;
     (void)zh_be::make_layout(n, prm, &fp.L);  // validated by the caller
+    if (zstd) zh_be::with_compressor(&fp.L, zh_be::ZstdCoder::kCode);
     fp.first_block = (int64_t)blocks.size();
     fp.first_stream = (int64_t)stream_raw.size();
     fp.raw_only = 4 * (size_t)fp.L.nblocks > n;
@@ -167,25 +262,40 @@ int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, zh_blosc_enc_frame* fram
       b.typesize = fp.L.typesize, b.shuffle = fp.L.shuffle;
       b.first_stream = (uint32_t)stream_raw.size();
       b.pad = 0;
-      for (uint32_t q = 0; q < b.nstreams; q++) stream_raw.push_back(b.size / b.nstreams);
+      const uint32_t neb = b.size / b.nstreams;
+      for (uint32_t q = 0; q < b.nstreams; q++) stream_raw.push_back(neb);
       blocks.push_back(b);
-      scratch_total += up(b.size, 16);
+      if (!zstd) {
+        scratch_total += up(b.size, 16);
+        continue;
+      }
+      for (uint32_t q = 0; q < b.nstreams; q++) {  // region: [headers | block], 16-byte aligned
+        zrows.push_back(
+            {0, (uint64_t)scratch_total + zh_be::kZstdHead, (uint64_t)seq_total, neb, 0});
+        scratch_total += up((int64_t)neb + zh_be::kZstdHead, 16);
+        seq_total += up(3 * (int64_t)(neb / 4) + 3, 8);
+      }
     }
     fp.nstreams = (int64_t)stream_raw.size() - fp.first_stream;
     compact_cap += up((int64_t)n + 16, 16);
     meta_cap += 16 + (fp.raw_only ? 0 : 4 * (int64_t)fp.L.nblocks);
-    njobs_cap += 1 + std::max<int64_t>(fp.nstreams, ((int64_t)n + kJobBytes - 1) / kJobBytes);
+    njobs_cap += 1 + std::max<int64_t>((zstd ? 2 : 1) * fp.nstreams,
+                                       ((int64_t)n + kJobBytes - 1) / kJobBytes);
   }
   if (blocks.size() > (size_t)zh::kIntMax || stream_raw.size() > (size_t)zh::kIntMax ||
       njobs_cap > zh::kIntMax)
     return ZH_EINVAL;
 
-  // device memory: [blocks | csizes | jobs | meta | scratch | compact]
+  // device memory: [blocks | csizes | jobs | meta | zrows | info | seqs | scratch | compact]
+  // (zrows, info and seqs: zstd streams only)
   const size_t o_blocks = 0;
   const size_t o_cs = (size_t)up((int64_t)(blocks.size() * sizeof(EncBlock)), 256);
   const size_t o_jobs = o_cs + (size_t)up((int64_t)stream_raw.size() * 4, 256);
   const size_t o_meta = o_jobs + (size_t)up(njobs_cap * (int64_t)sizeof(GatherJob), 256);
-  const size_t o_scratch = o_meta + (size_t)up(meta_cap, 256);
+  const size_t o_zrows = o_meta + (size_t)up(meta_cap, 256);
+  const size_t o_info = o_zrows + (size_t)up((int64_t)(zrows.size() * sizeof(ZBlock)), 256);
+  const size_t o_seq = o_info + (size_t)up((int64_t)zrows.size() * 8, 256);
+  const size_t o_scratch = o_seq + (size_t)up(seq_total * 2, 256);
   const size_t o_compact = o_scratch + (size_t)up(scratch_total, 256);
   const size_t need = o_compact + (size_t)compact_cap + 256;
   void* dmem = nullptr;
@@ -203,23 +313,39 @@ int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, zh_blosc_enc_frame* fram
   if (!blocks.empty()) {
     if (!ring.h2d(d8 + o_blocks, (const uint8_t*)blocks.data(), blocks.size() * sizeof(EncBlock)))
       rc = ZH_EHIP;
+    if (rc == ZH_OK && zstd &&
+        !ring.h2d(d8 + o_zrows, (const uint8_t*)zrows.data(), zrows.size() * sizeof(ZBlock)))
+      rc = ZH_EHIP;
     if (rc == ZH_OK) {
       if (timed) (void)hipEventRecord(ev[0], s);
       uint32_t cap = 0;
       for (const EncBlock& b : blocks) cap = std::max(cap, b.size);
-      auto kernel = cap <= (16u << 10)   ? blosc_encode_kernel<(16u << 10)>
-                    : cap <= (32u << 10) ? blosc_encode_kernel<(32u << 10)>
-                                         : blosc_encode_kernel<zh_be::kMaxBlock>;
-      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks.size()), dim3(kThreads), 0, s,
-                         (const EncBlock*)(d8 + o_blocks), d8 + o_scratch,
-                         (uint32_t*)(d8 + o_cs));
+      if (zstd) {
+        auto launch = cap <= (16u << 10)   ? launch_zstd<(16u << 10)>
+                      : cap <= (32u << 10) ? launch_zstd<(32u << 10)>
+                                           : launch_zstd<zh_be::kMaxBlock>;
+        launch(s, (unsigned)blocks.size(), (unsigned)zrows.size(),
+               (const EncBlock*)(d8 + o_blocks), (const ZBlock*)(d8 + o_zrows), dtab,
+               d8 + o_scratch, (uint16_t*)(d8 + o_seq), (uint32_t*)(d8 + o_info),
+               (uint32_t*)(d8 + o_cs));
+      } else {
+        auto kernel = cap <= (16u << 10)   ? blosc_encode_kernel<(16u << 10)>
+                      : cap <= (32u << 10) ? blosc_encode_kernel<(32u << 10)>
+                                           : blosc_encode_kernel<zh_be::kMaxBlock>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks.size()), dim3(kThreads), 0, s,
+                           (const EncBlock*)(d8 + o_blocks), d8 + o_scratch,
+                           (uint32_t*)(d8 + o_cs));
+      }
       if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
       if (timed) (void)hipEventRecord(ev[1], s);
     }
     if (rc == ZH_OK && !ring.d2h((uint8_t*)cs.data(), d8 + o_cs, cs.size() * 4)) rc = ZH_EHIP;
-    // the table lays out device copies: nothing in it may pass its stream's raw size
-    for (size_t k = 0; k < cs.size() && rc == ZH_OK; k++)
+    // the table lays out device copies: nothing in it may pass its stream's raw size (zstd: the
+    // table holds the sizes of the compressed blocks, the raw size where there is none)
+    for (size_t k = 0; k < cs.size() && rc == ZH_OK; k++) {
       if (cs[k] == 0 || cs[k] > stream_raw[k]) rc = ZH_EHIP;
+      if (zstd) cs[k] = zh_be::zstd_stream_size(stream_raw[k], cs[k]);
+    }
   }
 
   // layout: the frames side by side in the compact buffer, each 16-byte aligned
@@ -258,7 +384,21 @@ int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, zh_blosc_enc_frame* fram
           const uint32_t neb = b.size / b.nstreams;
           for (uint32_t q = 0; q < b.nstreams; q++) {
             const uint32_t c = cs[b.first_stream + q];
-            jobs.push_back({d_scratch + b.scratch + (uint64_t)q * neb, fbase + p, c, c, 4, 0});
+            if (!zstd) {
+              jobs.push_back({d_scratch + b.scratch + (uint64_t)q * neb, fbase + p, c, c, 4, 0});
+            } else {
+              // the stream's region: a raw stream, or [frame header | room | block]
+              const uint64_t blk = d_scratch + zrows[b.first_stream + q].out;
+              const uint64_t reg = blk - zh_be::kZstdHead;
+              if (c == neb) {
+                jobs.push_back({reg, fbase + p, c, c, 4, 0});
+              } else {
+                const uint32_t fh = (uint32_t)zh_ze::kFrameHeader, bsz = c - zh_be::kZstdHead;
+                jobs.push_back({reg, fbase + p, fh, c, 4, 0});
+                jobs.push_back({blk, fbase + p + 4 + fh, bsz, zh_ze::block_header(bsz, 2, true),
+                                3, 0});
+              }
+            }
             p += 4 + (size_t)c;
           }
         }
@@ -311,6 +451,7 @@ int64_t bound_of(const zh_blosc_enc_frame* frames, int64_t n, const zh_blosc_enc
   return total;
 }
 
+constexpr const char* kBadFlags = "blosc encode: unknown flag (ZH_BLOSC_ENC_ZSTD is the only one)";
 constexpr const char* kBadParams =
     "blosc encode: typesize 1..255, shuffle 0..2, blocksize >= 0, frames of at most 2 GiB";
 
@@ -318,18 +459,40 @@ constexpr const char* kBadParams =
 
 extern "C" {
 
-int zh_blosc_compress(const void* src, size_t n, const zh_blosc_enc_params* params, void* dst,
-                      size_t cap, size_t* cbytes, char* err, size_t errlen) {
+int zh_blosc_compress_ex(const void* src, size_t n, const zh_blosc_enc_params* params,
+                         unsigned flags, void* dst, size_t cap, size_t* cbytes, char* err,
+                         size_t errlen) {
+  if (flags & ~ZH_BLOSC_ENC_ZSTD) {
+    put_err(err, errlen, kBadFlags);
+    return ZH_EINVAL;
+  }
   size_t cb = 0;
   const char* msg = "";
-  const int st = zh_be::compress_frame((const uint8_t*)src, n, params, (uint8_t*)dst, cap, &cb,
-                                       &msg);
+  int st;
+  try {
+    if (flags & ZH_BLOSC_ENC_ZSTD) {
+      zh_be::ZstdCoder coder(zh_ze::tables());
+      st = zh_be::compress_frame((const uint8_t*)src, n, params, (uint8_t*)dst, cap, &cb, &msg,
+                                 coder);
+    } else {
+      zh_be::Lz4Coder coder;
+      st = zh_be::compress_frame((const uint8_t*)src, n, params, (uint8_t*)dst, cap, &cb, &msg,
+                                 coder);
+    }
+  } catch (const std::bad_alloc&) {
+    st = ZH_ENOMEM, msg = "zh_blosc_compress: out of memory";
+  }
   if (st != ZH_OK) {
     put_err(err, errlen, msg);
     return st;
   }
   if (cbytes) *cbytes = cb;
   return ZH_OK;
+}
+
+int zh_blosc_compress(const void* src, size_t n, const zh_blosc_enc_params* params, void* dst,
+                      size_t cap, size_t* cbytes, char* err, size_t errlen) {
+  return zh_blosc_compress_ex(src, n, params, 0, dst, cap, cbytes, err, errlen);
 }
 
 int64_t zh_blosc_encode_bound(const zh_blosc_enc_frame* frames, int64_t n,
@@ -342,7 +505,18 @@ double zh_debug_blosc_encode_kernel_ms(void) { return g_last_enc_ms.load(); }
 int zh_blosc_encode_batch(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
                           const zh_blosc_enc_params* params, void* dst, int64_t dstcap,
                           void* stream_v, char* err, size_t errlen) {
+  return zh_blosc_encode_batch_ex(ctx, frames, n, params, 0, dst, dstcap, stream_v, err, errlen);
+}
+
+int zh_blosc_encode_batch_ex(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
+                             const zh_blosc_enc_params* params, unsigned flags, void* dst,
+                             int64_t dstcap, void* stream_v, char* err, size_t errlen) {
   if (!ctx) return ZH_EINVAL;
+  if (flags & ~ZH_BLOSC_ENC_ZSTD) {
+    for (int64_t i = 0; i < n && frames; i++) frames[i].status = ZH_EINVAL;
+    put_err(err, errlen, kBadFlags);
+    return ZH_EINVAL;
+  }
   const int64_t bound = bound_of(frames, n, params);
   if (bound < 0) {
     for (int64_t i = 0; i < n && frames; i++) frames[i].status = ZH_EINVAL;
@@ -357,15 +531,16 @@ int zh_blosc_encode_batch(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
   std::lock_guard<std::mutex> lk(ctx->mu);
   (void)hipSetDevice(ctx->device);
   hipStream_t s = stream_v ? (hipStream_t)stream_v : ctx->stream;
+  const zh_ze::Tables* dtab = (flags & ZH_BLOSC_ENC_ZSTD) ? device_tables(ctx) : nullptr;
   Ring ring;
-  int rc = ring.init(ctx, s);
+  int rc = (flags & ZH_BLOSC_ENC_ZSTD) && !dtab ? ZH_ENOMEM : ring.init(ctx, s);
   int64_t pos = 0;
   double ms = 0;
   for (int64_t f0 = 0; f0 < n && rc == ZH_OK;) {
     int64_t f1 = f0, raw = 0;
     do raw += frames[f1++].nbytes;
     while (f1 < n && raw + frames[f1].nbytes <= kSlabBytes);
-    rc = encode_slab(ctx, s, ring, frames, f0, f1, params, (uint8_t*)dst, &pos, &ms);
+    rc = encode_slab(ctx, s, ring, frames, f0, f1, params, dtab, (uint8_t*)dst, &pos, &ms);
     f0 = f1;
   }
   if (rc != ZH_OK) {

@@ -61,7 +61,7 @@ struct zh_ctx {
   uint8_t* hout_pin = nullptr;
   bool hout_pin_failed = false;
   // the zstd writer's encoding tables (zh_ze::Tables) in device memory, uploaded on first use
-  // under mu (zh_zstd_enc_kernels.hip)
+  // under mu (device_tables, zh_enc_device.h: the zstd and the blosc zstd writers)
   void* zstd_tables = nullptr;
 };
 

@@ -1,8 +1,9 @@
 // zh_enc_device.h — what the device frame writers share (zh_blosc_enc_kernels.hip,
-// zh_zstd_enc_kernels.hip): the wave form of the lane policy of zh_lz_match.h, the gather kernel
-// that lays finished pieces out as compact frames, and the copies through the context's
-// page-locked rings.  Device code: included by .hip files only, each of which gets its own copy
-// (anonymous namespace).
+// zh_zstd_enc_kernels.hip): the wave form of the lane policy of zh_lz_match.h, the second phase
+// of the zstd block writer (zstd_fse_kernel over ZBlock rows, with the encoding tables in device
+// memory), the gather kernel that lays finished pieces out as compact frames, and the copies
+// through the context's page-locked rings.  Device code: included by .hip files only, each of
+// which gets its own copy (anonymous namespace).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +14,7 @@
 
 #include "zh_ctx.h"
 #include "zh_lz_match.h"
+#include "zh_zstd_enc.h"
 
 namespace {
 
@@ -131,6 +133,50 @@ __global__ __launch_bounds__(kThreads) void blosc_gather_kernel(
     }
   }
   for (uint32_t q = nv * 16 + t; q < n; q += kThreads) d[q] = s[q];
+}
+
+// One block of the zstd block writer (zh_zstd_enc.h): a block of a zstd frame, or a stream of a
+// blosc frame whose streams are zstd frames.
+struct ZBlock {
+  uint64_t src;      // device address of the raw block (the blosc writer: unused)
+  uint64_t out;      // offset of the block's region in the scratch buffer
+  uint64_t seq;      // offset of the block's records in the list, in uint16
+  uint32_t size, pad;
+};
+
+// One thread per block: zh_ze::fse_block walks the block's records backwards and writes the
+// sequences section behind the literals; the size of the compressed block (or the raw size:
+// store it raw) goes to a table.  The records and literals were written by the kernel before:
+// the kernel boundary orders them.  (The gzip writer includes this header and does not launch it.)
+[[maybe_unused]] __global__ __launch_bounds__(64) void zstd_fse_kernel(
+    const ZBlock* __restrict__ blocks, uint32_t nblocks, const zh_ze::Tables* __restrict__ tg,
+    uint8_t* __restrict__ scratch, const uint16_t* __restrict__ seqs,
+    const uint32_t* __restrict__ info, uint32_t* __restrict__ csize) {
+  __shared__ zh_ze::Tables T;
+  for (uint32_t i = threadIdx.x; i < sizeof(zh_ze::Tables) / 4; i += 64)
+    ((uint32_t*)&T)[i] = ((const uint32_t*)tg)[i];
+  __syncthreads();
+  const uint32_t k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= nblocks) return;
+  const ZBlock b = blocks[k];
+  csize[k] = zh_ze::fse_block(T, seqs + b.seq, info[2 * k], info[2 * k + 1], scratch + b.out,
+                              b.size);
+}
+static_assert(sizeof(zh_ze::Tables) % 4 == 0, "the tables are copied as words");
+
+// The encoding tables in device memory, uploaded once per context (under ctx->mu).
+inline const zh_ze::Tables* device_tables(zh_ctx* ctx) {
+  if (!ctx->zstd_tables) {
+    void* p = nullptr;
+    if (hipMalloc(&p, sizeof(zh_ze::Tables)) != hipSuccess) return nullptr;
+    if (hipMemcpy(p, &zh_ze::tables(), sizeof(zh_ze::Tables), hipMemcpyHostToDevice) !=
+        hipSuccess) {
+      (void)hipFree(p);
+      return nullptr;
+    }
+    ctx->zstd_tables = p;
+  }
+  return (const zh_ze::Tables*)ctx->zstd_tables;
 }
 
 void put_err(char* err, size_t errlen, const char* msg) {

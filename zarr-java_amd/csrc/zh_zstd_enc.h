@@ -196,12 +196,12 @@ inline uint32_t block_size(size_t n, uint32_t B, size_t k) {
   const size_t rest = n - k * B;
   return rest < B ? (uint32_t)rest : B;
 }
-inline void put_frame_header(uint8_t* d, size_t n, bool checksum) {
+ZH_BS_HD void put_frame_header(uint8_t* d, size_t n, bool checksum) {
   d[0] = 0x28, d[1] = 0xB5, d[2] = 0x2F, d[3] = 0xFD;
   d[4] = (uint8_t)((3u << 6) | (1u << 5) | (checksum ? 4u : 0u));  // 8-byte FCS, single segment
   for (int i = 0; i < 8; i++) d[5 + i] = (uint8_t)((uint64_t)n >> (8 * i));
 }
-inline uint32_t block_header(uint32_t size, uint32_t type, bool last) {
+ZH_BS_HD uint32_t block_header(uint32_t size, uint32_t type, bool last) {
   return (size << 3) | (type << 1) | (last ? 1u : 0u);
 }
 

@@ -10,7 +10,7 @@
 //           buffer (behind the 3 bytes of the literals header), sequence records to the block's
 //           part of the list, both in global memory, neither read again in this kernel.  The
 //           kernel has no barrier: between steps a wave waits for its own LDS operations only.
-//   zstd_fse_kernel     one thread per block: zh_ze::fse_block walks the block's records
+//   zstd_fse_kernel (zh_enc_device.h)   one thread per block: zh_ze::fse_block walks the records
 //           backwards and writes the sequences section behind the literals; the size of the
 //           compressed block (or the raw size: store it raw) goes to a table.  The records and
 //           literals were written by the kernel before: the kernel boundary orders them.
@@ -44,14 +44,7 @@
 namespace {
 
 constexpr int64_t kSlabBytes = (int64_t)128 << 20;
-static_assert(sizeof(zh_ze::Tables) % 4 == 0, "the tables are copied as words");
 
-struct ZBlock {
-  uint64_t src;      // device address of the raw block
-  uint64_t out;      // offset of the block's region in the scratch buffer
-  uint64_t seq;      // offset of the block's records in the list, in uint16
-  uint32_t size, pad;
-};
 struct HashJob {
   uint64_t src, n;
 };
@@ -93,21 +86,6 @@ __global__ __launch_bounds__(WAVES * 64) void zstd_match_kernel(
     info[2 * k] = ns;
     info[2 * k + 1] = nl;
   }
-}
-
-__global__ __launch_bounds__(64) void zstd_fse_kernel(
-    const ZBlock* __restrict__ blocks, uint32_t nblocks, const zh_ze::Tables* __restrict__ tg,
-    uint8_t* __restrict__ scratch, const uint16_t* __restrict__ seqs,
-    const uint32_t* __restrict__ info, uint32_t* __restrict__ csize) {
-  __shared__ zh_ze::Tables T;
-  for (uint32_t i = threadIdx.x; i < sizeof(zh_ze::Tables) / 4; i += 64)
-    ((uint32_t*)&T)[i] = ((const uint32_t*)tg)[i];
-  __syncthreads();
-  const uint32_t k = blockIdx.x * 64 + threadIdx.x;
-  if (k >= nblocks) return;
-  const ZBlock b = blocks[k];
-  csize[k] = zh_ze::fse_block(T, seqs + b.seq, info[2 * k], info[2 * k + 1], scratch + b.out,
-                              b.size);
 }
 
 // ---- XXH64, seed 0 ----------------------------------------------------------------------------
@@ -215,21 +193,6 @@ __global__ __launch_bounds__(kThreads) void zstd_xxh64_kernel(const HashJob* __r
 }
 
 std::atomic<double> g_last_zenc_ms{-1.0};
-
-// The encoding tables in device memory, uploaded once per context (under ctx->mu).
-const zh_ze::Tables* device_tables(zh_ctx* ctx) {
-  if (!ctx->zstd_tables) {
-    void* p = nullptr;
-    if (hipMalloc(&p, sizeof(zh_ze::Tables)) != hipSuccess) return nullptr;
-    if (hipMemcpy(p, &zh_ze::tables(), sizeof(zh_ze::Tables), hipMemcpyHostToDevice) !=
-        hipSuccess) {
-      (void)hipFree(p);
-      return nullptr;
-    }
-    ctx->zstd_tables = p;
-  }
-  return (const zh_ze::Tables*)ctx->zstd_tables;
-}
 
 void launch_match(uint32_t B, hipStream_t s, const ZBlock* blocks, uint32_t nblocks,
                   uint8_t* scratch, uint16_t* seqs, uint32_t* info) {

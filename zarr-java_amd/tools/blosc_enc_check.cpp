@@ -48,7 +48,8 @@ int main(int argc, char** argv) {
     uint8_t* frame = (uint8_t*)malloc(len + 16);
     size_t cbytes = 0;
     const char* msg = "";
-    int st = zh_be::compress_frame(buf, len, &prm, frame, len + 16, &cbytes, &msg);
+    zh_be::Lz4Coder lz4;
+    int st = zh_be::compress_frame(buf, len, &prm, frame, len + 16, &cbytes, &msg, lz4);
     const char* verdict = msg;
     if (st == ZH_OK) {
       // the decoder sees exactly cbytes

@@ -108,6 +108,11 @@ _SIGS = {
     "zh_blosc_encode_batch": (C.c_int, [P, C.POINTER(A.zh_blosc_enc_frame), I64,
                                         C.POINTER(A.zh_blosc_enc_params), P, I64, P, CH, SZ]),
     "zh_debug_blosc_encode_kernel_ms": (C.c_double, []),
+    "zh_blosc_compress_ex": (C.c_int, [P, SZ, C.POINTER(A.zh_blosc_enc_params), C.c_uint, P, SZ,
+                                       C.POINTER(SZ), CH, SZ]),
+    "zh_blosc_encode_batch_ex": (C.c_int, [P, C.POINTER(A.zh_blosc_enc_frame), I64,
+                                           C.POINTER(A.zh_blosc_enc_params), C.c_uint, P, I64, P,
+                                           CH, SZ]),
     "zh_zstd_decompress": (C.c_int, [P, SZ, P, SZ, C.POINTER(SZ), C.c_char_p, SZ]),
     "zh_zstd_compress_raw": (C.c_int, [P, SZ, C.c_int, P, SZ, C.POINTER(SZ)]),
     "zh_xxh64": (U64, [P, SZ, U64]),
@@ -546,10 +551,12 @@ class DeviceContext:
                 arr[i].host_only = 1
 
     def blosc_encode_batch_raw(self, sources, typesize, shuffle, blocksize=0, stream=None,
-                               take=None):
+                               take=None, zstd=False, flags=None):
         """zh_blosc_encode_bound + zh_blosc_encode_batch over (device address, nbytes) pairs:
         (the host buffer the frames arrived in, [(dst_off, cbytes)] per source).  `take(n)`: a
-        uint8 array of n bytes to receive them (default: a fresh one)."""
+        uint8 array of n bytes to receive them (default: a fresh one).  zstd: the streams are
+        zstd frames (zh_blosc_encode_batch_ex with ZH_BLOSC_ENC_ZSTD); flags: the flags word of
+        that call as it is."""
         import numpy as np
         n = len(sources)
         arr = (A.zh_blosc_enc_frame * max(1, n))()
@@ -562,15 +569,23 @@ class DeviceContext:
                                        "blocksize >= 0, frames of at most 2 GiB")
         out = (take or (lambda k: np.empty(k, np.uint8)))(max(1, bound))
         err = C.create_string_buffer(1024)
-        check(self.L.zh_blosc_encode_batch(self.h, arr, n, C.byref(prm), P(out.ctypes.data),
-                                           bound, P(stream), err, 1024), err)
+        if flags is None:
+            flags = A.ZH_BLOSC_ENC_ZSTD if zstd else 0
+        if flags == 0:
+            st = self.L.zh_blosc_encode_batch(self.h, arr, n, C.byref(prm), P(out.ctypes.data),
+                                              bound, P(stream), err, 1024)
+        else:
+            st = self.L.zh_blosc_encode_batch_ex(self.h, arr, n, C.byref(prm), int(flags),
+                                                 P(out.ctypes.data), bound, P(stream), err, 1024)
+        check(st, err)
         return out, [(int(arr[i].dst_off), int(arr[i].cbytes)) for i in range(n)]
 
     def blosc_encode_batch(self, sources, typesize, shuffle, blocksize=0, stream=None,
-                           take=None):
-        """The blosc1 LZ4 frames of (device address, nbytes) sources as a list of bytes."""
+                           take=None, zstd=False):
+        """The blosc1 frames (LZ4 streams; zstd: zstd streams) of (device address, nbytes)
+        sources as a list of bytes."""
         out, rows = self.blosc_encode_batch_raw(sources, typesize, shuffle, blocksize, stream,
-                                                take)
+                                                take, zstd)
         mv = memoryview(out)
         return [bytes(mv[o:o + n]) for o, n in rows]
 
@@ -958,17 +973,25 @@ def gzip_encode_kernel_parts_ms():
     return dict(zip(("match", "coder", "crc", "gather"), (float(v) for v in out)))
 
 
-def blosc_compress(data, typesize, shuffle, blocksize=0):
+def blosc_compress(data, typesize, shuffle, blocksize=0, zstd=False, flags=None):
     """zh_blosc_compress (no device): one blosc1 LZ4 frame of `data` (shuffle 0 none, 1 byte,
-    2 bit)."""
+    2 bit).  zstd: zh_blosc_compress_ex with ZH_BLOSC_ENC_ZSTD, the frame's streams are zstd
+    frames; flags: the flags word of that call as it is."""
     L = lib()
     data = bytes(data)
     prm = A.zh_blosc_enc_params(int(typesize), int(shuffle), int(blocksize))
     err = C.create_string_buffer(1024)
     out = C.create_string_buffer(len(data) + 16)
     n = C.c_size_t()
-    check(L.zh_blosc_compress(data, len(data), C.byref(prm), out, len(data) + 16, C.byref(n), err,
-                              1024), err)
+    if flags is None:
+        flags = A.ZH_BLOSC_ENC_ZSTD if zstd else 0
+    if flags == 0:
+        st = L.zh_blosc_compress(data, len(data), C.byref(prm), out, len(data) + 16, C.byref(n),
+                                 err, 1024)
+    else:
+        st = L.zh_blosc_compress_ex(data, len(data), C.byref(prm), int(flags), out,
+                                    len(data) + 16, C.byref(n), err, 1024)
+    check(st, err)
     return out.raw[:n.value]
 
 

@@ -15,7 +15,8 @@ host stage (ZH_BLOSC_DEVICE, zh_blosc_decode_batch; ZH_ZSTD_DEVICE, zh_zstd_deco
 ZH_GZIP_DEVICE, zh_gzip_decode_batch), and blosc LZ4 and zstd frames, which Array.write
 compresses on the device (ZH_BLOSC_ENCODE_DEVICE, zh_blosc_encode_batch; ZH_ZSTD_ENCODE_DEVICE,
 zh_zstd_encode_batch), as it does gzip members when asked to (ZH_GZIP_ENCODE_DEVICE=1, or 2
-for dynamic-Huffman segments as well; zh_gzip_encode_batch).
+for dynamic-Huffman segments as well; zh_gzip_encode_batch) and blosc frames with zstd streams
+(ZH_BLOSC_ZSTD_ENCODE=1; zh_blosc_encode_batch_ex).
 """
 import atexit
 import ctypes as C
@@ -69,6 +70,11 @@ GZIP_DEVICE_MIN_FRAMES = None
 # It stays "1" whatever the write times say: the stored size is what the codec was asked for,
 # and both routes store the same bytes (DESIGN.md "Blosc frames encoded on the device").
 BLOSC_ENCODE_DEVICE_DEFAULT = "1"
+# ZH_BLOSC_ZSTD_ENCODE (read by BloscCodec, codecs.py; default "0"): "1" compresses a blosc chain
+# whose cname is zstd, the codec's default, with zstd streams (zh_blosc_compress_ex /
+# zh_blosc_encode_batch_ex with ZH_BLOSC_ENC_ZSTD) on the route ZH_BLOSC_ENCODE_DEVICE names;
+# unset, such a chain is stored as MEMCPYED frames.  It is opt-in because it changes stored bytes
+# (DESIGN.md "Blosc zstd frames encoded on the device").
 # ZH_ZSTD_ENCODE_DEVICE: the same for a zstd chain (zh_zstd_encode_batch), and "1" for the same
 # reason (DESIGN.md "Zstd frames encoded on the device").
 ZSTD_ENCODE_DEVICE_DEFAULT = "1"
@@ -962,14 +968,14 @@ class Array:
         (ZH_BLOSC_ENCODE_DEVICE / ZH_ZSTD_ENCODE_DEVICE) is not "0", or, for gzip, whose host
         route is zlib and stores other bytes, ZH_GZIP_ENCODE_DEVICE is "1" or "2" ("2": with
         dynamic-Huffman segments, _gzip_dynamic).  Blosc: its cname is
-        lz4 / lz4hc (the one blosc compressor written here; clevel is not honoured, as the level
-        of zstd and gzip is not)."""
+        lz4 / lz4hc, or zstd with ZH_BLOSC_ZSTD_ENCODE=1 (the blosc compressors written here;
+        clevel is not honoured, as the level of zstd and gzip is not)."""
         if len(devices()) != 1:
             return None
         bb = self.chain.inner_host_bb if self.chain.chain["sharded"] else self.chain.host_bb
         if self._blosc_chain():
             on = os.environ.get("ZH_BLOSC_ENCODE_DEVICE", BLOSC_ENCODE_DEVICE_DEFAULT) != "0"
-            return "blosc" if on and bb[0].lz4() else None
+            return "blosc" if on and bb[0].compressed() else None
         if self._zstd_chain():
             on = os.environ.get("ZH_ZSTD_ENCODE_DEVICE", ZSTD_ENCODE_DEVICE_DEFAULT) != "0"
             return "zstd" if on else None
@@ -993,9 +999,11 @@ class Array:
         codec = (self.chain.inner_host_bb if sharded else self.chain.host_bb)[0]
         if kind == "blosc":
             ts, shuffle, blocksize = codec.enc_params(self.metadata.data_type.getByteCount())
+            zstd = codec.zstd_enc()
 
             def batch(sources, take):
-                return dev.blosc_encode_batch(sources, ts, shuffle, blocksize, take=take)
+                return dev.blosc_encode_batch(sources, ts, shuffle, blocksize, take=take,
+                                              zstd=zstd)
         elif kind == "zstd":
             def batch(sources, take):
                 return dev.zstd_encode_batch(sources, bool(codec.checksum), take=take)

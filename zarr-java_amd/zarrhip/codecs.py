@@ -14,6 +14,7 @@ frames of a chain whose only such stage is blosc, zstd or gzip to the device in 
 involved then.
 """
 import gzip as _gzip
+import os
 import struct
 import zlib
 
@@ -274,10 +275,15 @@ class BloscCodec(Codec):
     streams; with ZH_BLOSC_ZSTD_DEVICE=1 also frames whose streams are plain zstd frames, the
     default cname's; zlib payloads stay with zh_blosc_decompress).  encode compresses cname lz4 / lz4hc with the library's own
     LZ4 writer (zh_blosc_compress: byte-identical to the frames Array.write makes on the
-    device; clevel is not honoured, and blocks are at most 64 KiB); every other cname is
-    written as a MEMCPYED frame (no compressor for it here)."""
+    device; clevel is not honoured, and blocks are at most 64 KiB).  With ZH_BLOSC_ZSTD_ENCODE=1
+    cname zstd is compressed as well (zh_blosc_compress_ex with ZH_BLOSC_ENC_ZSTD: the LZ4
+    writer's layout with compressor code 4, every stream one zstd frame as zh_zstd_compress
+    writes it, or raw); the switch is off by default, since it changes stored bytes.  Every
+    other cname, and zstd with the switch unset, is written as a MEMCPYED frame (no compressor
+    for it here)."""
     name, kind = "blosc", "bb"
     SHUFFLE_CODE = {"noshuffle": 0, "shuffle": 1, "bitshuffle": 2}
+    ZSTD_ENCODE_DEFAULT = "0"
 
     def __init__(self, cname="zstd", clevel=5, shuffle="noshuffle", typesize=None, blocksize=0):
         self.cfg = {"typesize": typesize, "cname": cname, "clevel": clevel, "shuffle": shuffle,
@@ -304,6 +310,15 @@ class BloscCodec(Codec):
     def lz4(self):
         return self.cfg.get("cname") in ("lz4", "lz4hc")
 
+    def zstd_enc(self):
+        """cname zstd with ZH_BLOSC_ZSTD_ENCODE=1: encode writes zstd streams."""
+        return (self.cfg.get("cname") == "zstd" and
+                os.environ.get("ZH_BLOSC_ZSTD_ENCODE", self.ZSTD_ENCODE_DEFAULT) == "1")
+
+    def compressed(self):
+        """encode compresses (lz4 / lz4hc, or zstd behind its switch) and is not MEMCPYED."""
+        return self.lz4() or self.zstd_enc()
+
     def enc_params(self, default_typesize=1):
         """(typesize, shuffle code, blocksize) as zh_blosc_enc_params takes them."""
         return (self.cfg.get("typesize") or default_typesize,
@@ -312,10 +327,11 @@ class BloscCodec(Codec):
 
     def encode(self, b, default_typesize=1):
         b = bytes(b)
-        if self.lz4():
+        if self.compressed():
             from ._lib import ZhError, blosc_compress
             try:
-                return blosc_compress(b, *self.enc_params(default_typesize))
+                return blosc_compress(b, *self.enc_params(default_typesize),
+                                      zstd=self.zstd_enc())
             except ZhError as e:
                 raise ZarrException(f"Error in encoding blosc: {e}") from None
         ts = self.cfg.get("typesize") or 1
