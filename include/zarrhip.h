@@ -591,7 +591,8 @@ int zh_blosc_decompress(const void* src, size_t srclen, void* dst, size_t dstcap
  * streams: the compressed bytes cross PCIe and one kernel decodes every stream of the batch
  * (one workgroup per block, one wavefront per stream) and undoes the byte / bit shuffle.
  * Memcpyed frames are one copy; zlib and zstd payloads are decoded by zh_blosc_decompress on
- * the host and copied.  The decoded frames lie in one device buffer at dst_off. */
+ * the host and copied, unless the _ex calls below are given the flag that sends them to the
+ * device.  The decoded frames lie in one device buffer at dst_off. */
 typedef struct zh_blosc_frame {
   const void* src;   /* the stored frame, host memory                               */
   int64_t srclen;
@@ -638,11 +639,22 @@ int64_t zh_debug_blosc_streams(const void* src, size_t srclen, int64_t* rows, in
  * decoded one wavefront each by the library's zstd frame decoder into the block's window before
  * the kernel above undoes the shuffle; the diagnostic reports them with method 3.  Any other
  * zstd frame (a stream with a checksum, without or with another content size, concatenated or
- * skippable frames) stays where = 1.  zlib payloads stay on the host.  The device memory of one
- * launch is bounded: at most 128 MiB of decoded zstd frames go into one slab (a larger frame is
- * its own), and a slab's literal scratch and shuffle temporary are each at most its decoded
- * bytes.  zh_debug_blosc_kernel_ms covers both kernels of every slab. */
+ * skippable frames) stays where = 1.
+ * ZH_BLOSC_ZLIB_DEVICE: a frame with compressor code 3 (zlib) is planned where = 0 when its
+ * chain is sound and every stream is stored raw or begins with a zlib header that inflate
+ * accepts (CM 8, valid check bits, no preset dictionary) and that declares the 32 KiB window
+ * (CINFO 7: what compress2, which c-blosc calls, writes).  Such streams are decoded one wavefront
+ * each by the library's DEFLATE decoder, which also computes the Adler-32 of what it wrote; a
+ * stream is good when exactly its raw size came out and the Adler-32 is the stored one (bytes
+ * behind the trailer are ignored, as uncompress ignores them).  The diagnostic reports them with
+ * method 4.  A frame with any other stream stays where = 1.  Without its flag a compressor's
+ * payloads stay on the host.  The value is 4: 2 is not a flag.
+ * The device memory of one launch is bounded: at most 128 MiB of decoded zstd and zlib frames go
+ * into one slab (a larger frame is its own), and a slab's literal scratch and shuffle temporary
+ * are each at most its decoded bytes.  zh_debug_blosc_kernel_ms covers all kernels of every
+ * slab. */
 #define ZH_BLOSC_ZSTD_DEVICE 1u
+#define ZH_BLOSC_ZLIB_DEVICE 4u
 int64_t zh_blosc_batch_plan_ex(zh_blosc_frame* frames, int64_t n, unsigned flags, char* err,
                                size_t errlen);
 int zh_blosc_decode_batch_ex(zh_ctx* ctx, zh_blosc_frame* frames, int64_t n, unsigned flags,

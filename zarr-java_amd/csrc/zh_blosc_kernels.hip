@@ -1,6 +1,7 @@
 // zh_blosc_kernels.hip — batched device decode of blosc1 frames whose streams are LZ4, BloscLZ
 // or stored raw (zh_blosc_batch_plan / zh_blosc_decode_batch / zh_debug_blosc_streams), and, with
-// ZH_BLOSC_ZSTD_DEVICE through the _ex forms of those calls, plain zstd frames (below).
+// ZH_BLOSC_ZSTD_DEVICE / ZH_BLOSC_ZLIB_DEVICE through the _ex forms of those calls, plain zstd
+// frames and zlib streams (below).
 //
 // The host walks every frame once (zh_blosc_streams.h: build_table) into block and stream rows;
 // the compressed bytes cross PCIe through the context's page-locked ring; one kernel decodes:
@@ -62,6 +63,29 @@
 //   bounds  every pass-1 row is checked on the host against the staged bytes, the window it
 //           writes (destination or temporary) and the scratch before launch; decode_frame
 //           checks every read against csize and every write against rawsize / litcap.
+//
+// With ZH_BLOSC_ZLIB_DEVICE frames of compressor code 3 whose streams are raw or a zlib stream
+// with compress2's header (zh_bs::zlib_stream_head_ok) take the same two passes:
+//   pass 1  blosc_zlib_kernel, the shape of gzip_decode_kernel (zh_gzip_dec_kernels.hip): one wave
+//           per zlib stream of the slab, 4 streams per workgroup, no barrier, zh_gd::Work per wave
+//           in LDS (4 x 3 928 B = 15 712 B: ten workgroups per CU).  The wave runs
+//           zh_bs::zlib_stream with ZdLanes: zh_gd::decode_zlib_stream into the stream's place in
+//           the block's global window (the destination for an unshuffled block, the temporary for
+//           a shuffled one), then, behind order(), the Adler-32 of that window across its lanes
+//           (zh_gd::adler32: four bytes per lane and round, 64-bit partial sums, a wave
+//           reduction), compared with the stored one.  Acceptance is uncompress's, the host
+//           decoder's call: exactly rawsize bytes and a matching Adler-32; bytes behind the
+//           trailer are ignored.  A failing stream stores 1 to its frame's flag.
+//   pass 2  as for zstd frames: DevBlock::pass1 says that pass 1 wrote to the block's global
+//           window, kZlib streams are skipped like kZstd ones, and an unshuffled block of zlib
+//           streams only is finished by pass 1.
+//   order   the argument above: match copies and the Adler-32 load window bytes that other lanes
+//           of the same wave stored; the tables in Work are read by other lanes than wrote them.
+//   memory  decoded bytes of zlib device frames count towards the same kSlabBytes as zstd ones,
+//           which bounds the temporary; a zlib stream needs no literal scratch.
+//   bounds  every pass-1 row is checked on the host against the staged bytes and its window;
+//           decode_zlib_stream checks every read against csize and every write against rawsize,
+//           and adler32 reads [0, rawsize) of the window only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -83,13 +107,14 @@ using zh_bs::StreamRow;
 constexpr uint32_t kLdsBlock = 64u << 10;  // largest block decoded in LDS
 constexpr int kWaves = 4;
 constexpr int kThreads = kWaves * 64;
-constexpr int64_t kSlabBytes = (int64_t)128 << 20;  // decoded zstd frames of one slab
+constexpr int64_t kSlabBytes = (int64_t)128 << 20;  // decoded zstd / zlib frames of one slab
 
 struct DevBlock {
   int64_t dst_off;  // in the batch destination
   int64_t tmp_off;  // in the temporary (-1: none needed)
   uint32_t size, typesize, shuffle, first_stream, nstreams, frame;  // frame: in the slab
-  uint32_t zstd;    // a block of a zstd frame: its window is global memory, pass 1 wrote to it
+  uint32_t pass1;   // a block of a zstd or zlib frame: its window is global memory, pass 1 wrote
+                    // to it
   uint32_t pad;
 };
 struct DevStream {
@@ -101,6 +126,11 @@ struct DevZstd {     // a kZstd stream: a row of pass 1
   int64_t out_off;   // its place in the window: in the temporary (in_tmp) or the destination
   int64_t lit_off;   // in the literal scratch
   uint32_t csize, rawsize, litcap, frame, in_tmp, pad;
+};
+struct DevZlib {     // a kZlib stream: a row of pass 1
+  int64_t src_off;   // in the staged compressed bytes
+  int64_t out_off;   // its place in the window: in the temporary (in_tmp) or the destination
+  uint32_t csize, rawsize, frame, in_tmp;
 };
 
 // The copy policy of zh_bs::lz4_stream / blosclz_stream for one wave.
@@ -148,7 +178,8 @@ __device__ bool decode_block_streams(const uint8_t* __restrict__ src, const DevB
   c.lane = lane;
   for (uint32_t s = wave; s < b.nstreams; s += kWaves) {
     const DevStream r = streams[b.first_stream + s];
-    if (r.method == zh_bs::kZstd) continue;  // pass 1 left it in the (global) window
+    // pass 1 left it in the (global) window
+    if (r.method == zh_bs::kZstd || r.method == zh_bs::kZlib) continue;
     ok &= zh_bs::decode_stream(src + r.src_off, r.csize, (uint8_t*)(win + r.blk_off), r.rawsize,
                                r.method, c);
   }
@@ -181,7 +212,7 @@ __global__ __launch_bounds__(kThreads) void blosc_decode_kernel(
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   uint8_t* out = dst + b.dst_off;
   bool ok;
-  if (b.size <= kLdsBlock && !b.zstd) {  // uniform per workgroup
+  if (b.size <= kLdsBlock && !b.pass1) {  // uniform per workgroup
     ok = decode_block_streams(src, b, streams, &lds[0], wave, lane);
     if (!ok) flags[b.frame] = 1;
     __syncthreads();
@@ -221,6 +252,24 @@ __global__ __launch_bounds__(kThreads) void blosc_zstd_kernel(
   if (v && p.l == 0) flags[r.frame] = 1;
 }
 
+// Pass 1 of a zlib frame's blocks: one wave per kZlib stream, no barrier (a wave may return
+// alone).  zlib_stream: the DEFLATE blocks into the window, then the Adler-32 of the window.
+__global__ __launch_bounds__(kThreads) void blosc_zlib_kernel(
+    const uint8_t* __restrict__ src, uint8_t* dst, uint8_t* tmp, const DevZlib* __restrict__ rows,
+    uint32_t nrows, uint32_t* __restrict__ flags) {
+  __shared__ zh_gd::Work work[kWaves];
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t k = blockIdx.x * kWaves + wave;
+  if (k >= nrows) return;  // the whole wave
+  const DevZlib r = rows[k];
+  ZdLanes p;
+  p.l = threadIdx.x & 63;
+  // any verdict, another size than rawsize, another Adler-32 than the stored one
+  const zh_gd::Verdict v = zh_bs::zlib_stream(
+      src + r.src_off, r.csize, (r.in_tmp ? tmp : dst) + r.out_off, r.rawsize, work[wave], p);
+  if (v && p.l == 0) flags[r.frame] = 1;
+}
+
 void put_err(char* err, size_t errlen, const char* msg) {
   if (err && errlen) {
     strncpy(err, msg, errlen - 1);
@@ -233,7 +282,12 @@ std::atomic<double> g_last_kernel_ms{-1.0};
 constexpr int64_t kAlign = 256;
 inline int64_t up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
-constexpr unsigned kKnownFlags = ZH_BLOSC_ZSTD_DEVICE;
+constexpr unsigned kKnownFlags = ZH_BLOSC_ZSTD_DEVICE | ZH_BLOSC_ZLIB_DEVICE;
+
+// The flag that admits a host-decoded compressor code to the device plan (0: none does).
+inline unsigned device_flag(int comp) {
+  return comp == 4 ? ZH_BLOSC_ZSTD_DEVICE : comp == 3 ? ZH_BLOSC_ZLIB_DEVICE : 0u;
+}
 
 struct CountRows {  // build_table's rows, counted only
   size_t n = 0;
@@ -270,8 +324,8 @@ int plan_frames(zh_blosc_frame* frames, int64_t n, unsigned flags, int64_t* tota
     f.dst_off = pos;
     f.nbytes = (int64_t)h.nbytes;
     f.where = zh_bs::frame_where(h);
-    if (f.where == 1 && h.comp == 4 && (flags & ZH_BLOSC_ZSTD_DEVICE)) {
-      // a sound chain of raw streams and plain zstd frames: the device's
+    if (f.where == 1 && (flags & device_flag(h.comp))) {
+      // a sound chain of raw streams and plain zstd frames (or zlib streams): the device's
       CountRows cb, cs;
       if (zh_bs::build_table((const uint8_t*)f.src, (size_t)f.srclen, h, cb, cs, &msg, flags) ==
           ZH_OK)
@@ -309,6 +363,7 @@ int decode_slab(Batch& B, int64_t i0, int64_t i1, bool host_frames, const char**
   std::vector<DevBlock> blocks;
   std::vector<DevStream> streams;
   std::vector<DevZstd> zrows;
+  std::vector<DevZlib> lrows;
   std::vector<int64_t> src_base((size_t)ns, -1);
   int64_t src_total = 0, tmp_total = 0, lit_total = 0;
   {
@@ -331,7 +386,7 @@ int decode_slab(Batch& B, int64_t i0, int64_t i1, bool host_frames, const char**
         B.suspect[(size_t)i] = 1;  // nothing of it is decoded on the device
         continue;
       }
-      const bool zf = h.comp == 4;
+      const bool zf = h.comp == 4 || h.comp == 3;  // a frame with streams for pass 1
       src_base[(size_t)(i - i0)] = src_total;
       for (const BlockRow& b : fb) {
         DevBlock d;
@@ -345,11 +400,21 @@ int decode_slab(Batch& B, int64_t i0, int64_t i1, bool host_frames, const char**
         d.first_stream = (uint32_t)streams.size() + b.first_stream;
         d.nstreams = b.nstreams;
         d.frame = (uint32_t)(i - i0);
-        d.zstd = zf ? 1u : 0u;
+        d.pass1 = zf ? 1u : 0u;
         d.pad = 0;
         bool raw = false;
         for (uint32_t k = 0; k < b.nstreams; k++) {
           const StreamRow& r = fs[b.first_stream + k];
+          if (r.method == zh_bs::kZlib) {
+            DevZlib l;
+            l.src_off = src_total + r.src_off;
+            l.out_off = (d.tmp_off >= 0 ? d.tmp_off : d.dst_off) + (int64_t)r.blk_off;
+            l.csize = r.csize, l.rawsize = r.rawsize;
+            l.frame = d.frame;
+            l.in_tmp = d.tmp_off >= 0 ? 1u : 0u;
+            lrows.push_back(l);
+            continue;
+          }
           if (r.method != zh_bs::kZstd) {
             raw = true;
             continue;
@@ -365,7 +430,7 @@ int decode_slab(Batch& B, int64_t i0, int64_t i1, bool host_frames, const char**
           lit_total = up(lit_total + (int64_t)r.max_regen, 16);
           zrows.push_back(z);
         }
-        // an unshuffled block of zstd streams only is finished by pass 1
+        // an unshuffled block of zstd (or zlib) streams only is finished by pass 1
         if (!zf || raw || d.tmp_off >= 0) blocks.push_back(d);
       }
       for (const StreamRow& r : fs)
@@ -387,12 +452,22 @@ int decode_slab(Batch& B, int64_t i0, int64_t i1, bool host_frames, const char**
       return ZH_EINVAL;
     }
   }
+  for (const DevZlib& l : lrows) {
+    const int64_t room = l.in_tmp ? tmp_total : B.total;
+    if (l.src_off < 0 || l.src_off + (int64_t)l.csize > src_total || l.out_off < 0 ||
+        l.out_off + (int64_t)l.rawsize > room) {
+      *why = "zh_blosc_decode_batch: a stream row leaves its buffers";
+      return ZH_EINVAL;
+    }
+  }
 
-  // device memory: [streams | blocks | zstd rows | flags | compressed bytes | temporary | literals]
+  // device memory: [streams | blocks | zstd rows | zlib rows | flags | compressed bytes |
+  // temporary | literals]
   const size_t o_streams = 0;
   const size_t o_blocks = (size_t)up((int64_t)(streams.size() * sizeof(DevStream)), 256);
   const size_t o_zrows = o_blocks + (size_t)up((int64_t)(blocks.size() * sizeof(DevBlock)), 256);
-  const size_t o_flags = o_zrows + (size_t)up((int64_t)(zrows.size() * sizeof(DevZstd)), 256);
+  const size_t o_lrows = o_zrows + (size_t)up((int64_t)(zrows.size() * sizeof(DevZstd)), 256);
+  const size_t o_flags = o_lrows + (size_t)up((int64_t)(lrows.size() * sizeof(DevZlib)), 256);
   const size_t o_src = o_flags + (size_t)up(ns * 4, 256);
   const size_t o_tmp = o_src + (size_t)up(src_total, 256);
   const size_t o_lit = o_tmp + (size_t)up(tmp_total, 256);
@@ -417,7 +492,9 @@ int decode_slab(Batch& B, int64_t i0, int64_t i1, bool host_frames, const char**
     sg.append((const uint8_t*)blocks.data(), blocks.size() * sizeof(DevBlock));
     sg.skip(o_zrows - o_blocks - blocks.size() * sizeof(DevBlock));
     sg.append((const uint8_t*)zrows.data(), zrows.size() * sizeof(DevZstd));
-    sg.skip(o_flags - o_zrows - zrows.size() * sizeof(DevZstd));
+    sg.skip(o_lrows - o_zrows - zrows.size() * sizeof(DevZstd));
+    sg.append((const uint8_t*)lrows.data(), lrows.size() * sizeof(DevZlib));
+    sg.skip(o_flags - o_lrows - lrows.size() * sizeof(DevZlib));
     sg.append((const uint8_t*)flags.data(), (size_t)ns * 4);
     sg.skip(o_src - o_flags - (size_t)ns * 4);
     int64_t pos = 0;
@@ -448,7 +525,7 @@ int decode_slab(Batch& B, int64_t i0, int64_t i1, bool host_frames, const char**
         sg.copy(B.dst + f.dst_off, hostbuf.data(), (size_t)f.nbytes);
       }
     }
-    const bool work = !blocks.empty() || !zrows.empty();
+    const bool work = !blocks.empty() || !zrows.empty() || !lrows.empty();
     hipEvent_t k0 = nullptr, k1 = nullptr;
     if (work && hipEventCreate(&k0) == hipSuccess && hipEventCreate(&k1) == hipSuccess)
       (void)hipEventRecord(k0, s);
@@ -456,6 +533,11 @@ int decode_slab(Batch& B, int64_t i0, int64_t i1, bool host_frames, const char**
       hipLaunchKernelGGL(blosc_zstd_kernel, dim3((unsigned)((zrows.size() + kWaves - 1) / kWaves)),
                          dim3(kThreads), 0, s, d8 + o_src, B.dst, d8 + o_tmp, d8 + o_lit,
                          (const DevZstd*)(d8 + o_zrows), (uint32_t)zrows.size(),
+                         (uint32_t*)(d8 + o_flags));
+    if (!lrows.empty())
+      hipLaunchKernelGGL(blosc_zlib_kernel, dim3((unsigned)((lrows.size() + kWaves - 1) / kWaves)),
+                         dim3(kThreads), 0, s, d8 + o_src, B.dst, d8 + o_tmp,
+                         (const DevZlib*)(d8 + o_lrows), (uint32_t)lrows.size(),
                          (uint32_t*)(d8 + o_flags));
     if (!blocks.empty())
       hipLaunchKernelGGL(blosc_decode_kernel, dim3((unsigned)blocks.size()), dim3(kThreads), 0, s,
@@ -514,8 +596,8 @@ int64_t zh_debug_blosc_streams_ex(const void* src, size_t srclen, unsigned flags
   int st = zh_bs::parse_header((const uint8_t*)src, srclen, &h, &msg);
   std::vector<BlockRow> blocks;
   std::vector<StreamRow> streams;
-  const bool zstd = st == ZH_OK && !h.memcpyed && h.comp == 4 && (flags & ZH_BLOSC_ZSTD_DEVICE);
-  if (st == ZH_OK && zh_bs::frame_where(h) != 0 && !zstd) {
+  const bool admitted = st == ZH_OK && !h.memcpyed && (flags & device_flag(h.comp));
+  if (st == ZH_OK && zh_bs::frame_where(h) != 0 && !admitted) {
     st = ZH_EUNSUPPORTED;
     msg = h.memcpyed ? "blosc frame is memcpyed: it has no streams"
                      : "blosc payload is decoded on the host";
@@ -577,13 +659,13 @@ int zh_blosc_decode_batch_ex(zh_ctx* ctx, zh_blosc_frame* frames, int64_t n, uns
   B.dst = (uint8_t*)dst;
   B.suspect.assign((size_t)n, 0);
   B.bad.assign((size_t)n, 0);
-  // slabs: a zstd device frame that would take the slab's decoded zstd bytes past kSlabBytes
-  // opens the next one
+  // slabs: a zstd or zlib device frame that would take the slab's decoded bytes of such frames
+  // past kSlabBytes opens the next one
   int64_t i0 = 0, zraw = 0;
   bool first = true;
   for (int64_t i = 0; i <= n; i++) {
     const bool zf = i < n && frames[i].where == 0 && frames[i].nbytes > 0 &&
-                    (((const uint8_t*)frames[i].src)[2] >> 5) == 4;
+                    device_flag(((const uint8_t*)frames[i].src)[2] >> 5) != 0;
     if (i == n || (zf && zraw > 0 && zraw + frames[i].nbytes > kSlabBytes)) {
       const char* why = "";
       const int rc = decode_slab(B, i0, i, first, &why);

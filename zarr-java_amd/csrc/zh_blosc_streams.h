@@ -24,12 +24,17 @@
 //     ZH_BLOSC_ZSTD_DEVICE: a stream is then stored raw or ONE plain zstd frame (zstd_stream_ok),
 //     method kZstd, decoded by zh_zstd_dec.h's decode_frame and not by decode_stream.  Without
 //     the flag, or with any other kind of stream, the frame is the host decoder's.
+//   * zlib streams (compressor code 3) enter the table only when the caller passes
+//     ZH_BLOSC_ZLIB_DEVICE: a stream is then stored raw or a zlib stream whose two header bytes
+//     zlib_stream_head_ok accepts, method kZlib, decoded by zlib_stream (zh_gzip_dec.h's
+//     decode_zlib_stream and adler32) with the acceptance of zlib's uncompress.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/zarrhip.h"
+#include "zh_gzip_dec.h"
 #include "zh_zstd_dec.h"
 
 #if defined(__HIPCC__)
@@ -40,7 +45,7 @@
 
 namespace zh_bs {
 
-enum Method : uint32_t { kRaw = 0, kLz4 = 1, kBloscLz = 2, kZstd = 3 };
+enum Method : uint32_t { kRaw = 0, kLz4 = 1, kBloscLz = 2, kZstd = 3, kZlib = 4 };
 // kShufBit2: c-blosc 1.x (frame version <= 2) bit-shuffles a block only when its element count
 // is a multiple of 8; kShufBit3: later formats shuffle the multiple-of-8 prefix.
 enum Shuffle : uint32_t { kShufNone = 0, kShufByte = 1, kShufBit2 = 2, kShufBit3 = 3 };
@@ -245,7 +250,8 @@ inline int parse_header(const uint8_t* src, size_t srclen, Header* h, const char
 }
 
 // Where a frame is decoded: 0 device streams, 1 host (zlib / zstd payloads), 2 memcpyed.
-// (With ZH_BLOSC_ZSTD_DEVICE a zstd frame whose table build_table accepts is 0: the plan's.)
+// (With ZH_BLOSC_ZSTD_DEVICE a zstd frame whose table build_table accepts is 0, and with
+// ZH_BLOSC_ZLIB_DEVICE a zlib frame: the plan's.)
 inline int frame_where(const Header& h) {
   if (h.memcpyed) return 2;
   return (h.comp == 3 || h.comp == 4) ? 1 : 0;
@@ -262,16 +268,45 @@ inline bool zstd_stream_ok(const uint8_t* s, size_t n, size_t neb, uint32_t* max
   return true;
 }
 
+// What the device route takes of a zlib stream: a header zlib's inflate accepts (CM 8, the check
+// bits, no preset dictionary) that declares the 32 KiB window (CINFO 7: what compress2, which
+// c-blosc calls, writes), so that no zlib, however strictly it checks a distance against the
+// declared window, can disagree with the device about one.  Any other header is the host
+// decoder's to judge.
+inline bool zlib_stream_head_ok(const uint8_t* s, size_t n) {
+  uint32_t cinfo = 0;
+  return zh_gd::zlib_header(s, n, &cinfo) == zh_gd::kOk && cinfo == 7;
+}
+
+// One zlib stream (src, csize) -> (dst, rawsize) with the acceptance of zlib_block in
+// zh_blosc.cpp, which is uncompress's: exactly rawsize bytes come out and their Adler-32 is the
+// stored one; bytes behind the trailer are ignored.  All lanes of P return the same verdict.
+template <class P>
+ZH_BS_HD zh_gd::Verdict zlib_stream(const uint8_t* s, uint32_t n, uint8_t* d, uint32_t rawsize,
+                                    zh_gd::Work& w, P& p) {
+  uint64_t made = 0;
+  size_t used = 0;
+  uint32_t adler = 0;
+  zh_gd::Verdict v =
+      zh_gd::decode_zlib_stream(s, (size_t)n, d, (uint64_t)rawsize, w, p, &made, &used, &adler);
+  if (!v && made != (uint64_t)rawsize) v = zh_gd::kSizeMismatch;
+  if (v) return v;
+  p.order();  // the sums read what other lanes stored
+  return zh_gd::adler32(d, made, p) == adler ? zh_gd::kOk : zh_gd::kAdlerMismatch;
+}
+
 // Block and stream rows of a frame whose header parse_header accepted and that is neither
 // memcpyed nor host-decoded.  `flags`: ZH_BLOSC_ZSTD_DEVICE admits compressor code 4; a stream
 // zstd_stream_ok refuses makes the frame host-decoded (ZH_EUNSUPPORTED, as without the flag).
+// ZH_BLOSC_ZLIB_DEVICE admits compressor code 3 in the same way, with zlib_stream_head_ok.
 // V: a vector-like with push_back / size.  Walks the frame as zh_blosc_decompress does; at the first field that fails returns that decoder's status and
 // text with the rows of the blocks before it in place (the failing block's rows are dropped).
 template <class VB, class VS>
 inline int build_table(const uint8_t* src, size_t srclen, const Header& h, VB& blocks,
                        VS& streams, const char** msg, unsigned flags = 0) {
   const bool zstd = h.comp == 4 && (flags & ZH_BLOSC_ZSTD_DEVICE);
-  if (h.comp != 0 && h.comp != 1 && !zstd) {
+  const bool zlib = h.comp == 3 && (flags & ZH_BLOSC_ZLIB_DEVICE);
+  if (h.comp != 0 && h.comp != 1 && !zstd && !zlib) {
     *msg = h.comp == 2 ? "blosc compressor (snappy) not available on this host"
                        : "blosc payload is decoded on the host";
     return ZH_EUNSUPPORTED;
@@ -313,9 +348,10 @@ inline int build_table(const uint8_t* src, size_t srclen, const Header& h, VB& b
       r.csize = (uint32_t)cs;
       r.blk_off = (uint32_t)(sidx * neb);
       r.rawsize = (uint32_t)neb;
-      r.method = cs == neb ? kRaw : zstd ? kZstd : (h.comp == 0 ? kBloscLz : kLz4);
+      r.method = cs == neb ? kRaw : zstd ? kZstd : zlib ? kZlib : (h.comp == 0 ? kBloscLz : kLz4);
       r.max_regen = 0;
-      if (r.method == kZstd && !zstd_stream_ok(src + p, cs, neb, &r.max_regen)) {
+      if ((r.method == kZstd && !zstd_stream_ok(src + p, cs, neb, &r.max_regen)) ||
+          (r.method == kZlib && !zlib_stream_head_ok(src + p, cs))) {
         *msg = "blosc payload is decoded on the host";
         return ZH_EUNSUPPORTED;
       }
@@ -329,9 +365,12 @@ inline int build_table(const uint8_t* src, size_t srclen, const Header& h, VB& b
 
 // zh_blosc_decompress for frames with raw / LZ4 / BloscLZ streams, through the tables and the
 // serial form of the shared parser.  `tmp`: scratch of at least min(blocksize, nbytes) bytes.
+// `flags`: with ZH_BLOSC_ZLIB_DEVICE also the frames with zlib streams that build_table admits
+// (zlib_stream on one lane); the other flags mean nothing here.
 template <class VB, class VS>
 inline int decode_frame_serial(const uint8_t* src, size_t srclen, uint8_t* dst, size_t dstcap,
-                               uint8_t* tmp, VB& blocks, VS& streams, const char** msg) {
+                               uint8_t* tmp, VB& blocks, VS& streams, const char** msg,
+                               unsigned flags = 0) {
   Header h;
   int st = parse_header(src, srclen, &h, msg);
   if (st != ZH_OK) return st;
@@ -345,18 +384,26 @@ inline int decode_frame_serial(const uint8_t* src, size_t srclen, uint8_t* dst, 
   }
   const size_t b0 = blocks.size();
   const char* tmsg = nullptr;
-  const int tst = build_table(src, srclen, h, blocks, streams, &tmsg);
+  const int tst =
+      build_table(src, srclen, h, blocks, streams, &tmsg, flags & ZH_BLOSC_ZLIB_DEVICE);
   if (tst == ZH_EUNSUPPORTED) {
     *msg = tmsg;
     return tst;
   }
   SerialCopy c;
+  zh_gd::SerialLanes lanes;
+  zh_gd::Work work;  // kZlib streams only
   for (size_t k = b0; k < blocks.size(); k++) {
     const BlockRow& b = blocks[k];
     uint8_t* out = b.shuffle == kShufNone ? dst + b.dst_off : tmp;
     for (uint32_t s = 0; s < b.nstreams; s++) {
       const StreamRow& r = streams[b.first_stream + s];
-      if (!decode_stream(src + r.src_off, r.csize, out + r.blk_off, r.rawsize, r.method, c)) {
+      const bool ok =
+          r.method == kZlib
+              ? zlib_stream(src + r.src_off, r.csize, out + r.blk_off, r.rawsize, work, lanes) ==
+                    zh_gd::kOk
+              : decode_stream(src + r.src_off, r.csize, out + r.blk_off, r.rawsize, r.method, c);
+      if (!ok) {
         *msg = "corrupt blosc block";
         return ZH_EDATA;
       }

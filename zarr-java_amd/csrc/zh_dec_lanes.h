@@ -43,6 +43,12 @@ struct ZdLanes {
   __device__ void spread(uint8_t* d, uint32_t v, uint32_t n) {
     if (l < n) d[l] = (uint8_t)v;
   }
+  // the Adler-32 step of a zlib stream: the wave's sum in every lane (a butterfly of six
+  // cross-lane exchanges; no memory)
+  __device__ uint32_t sum(uint32_t v) {
+    for (int m = 32; m > 0; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
+    return v;
+  }
 };
 
 }  // namespace

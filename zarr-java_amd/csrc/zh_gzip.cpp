@@ -59,6 +59,11 @@ const Text& text_of(zh_gd::Verdict v) {
     {kSizeMismatch, ZH_EDATA, "gzip: incorrect length check"},
     {kCrcMismatch, ZH_EDATA, "gzip: incorrect data check"},
     {kNotToTheEnd, ZH_EDATA, "gzip: bytes after the member"},
+    // a zlib stream's (decode_zlib_stream): no gzip member is rejected for these
+    {kZlibHeader, ZH_EDATA, "zlib: incorrect header check"},
+    {kZlibDictionary, ZH_EDATA, "zlib: need dictionary"},
+    {kZlibTrailerTruncated, ZH_EDATA, "zlib: trailer truncated"},
+    {kAdlerMismatch, ZH_EDATA, "zlib: incorrect data check"},
   };
   static_assert(sizeof T / sizeof T[0] == kVerdicts - 1, "a reason without a text");
   for (const Text& t : T)

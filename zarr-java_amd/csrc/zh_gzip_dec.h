@@ -18,6 +18,12 @@
 //            bytes produced so far is rejected.
 //   trailer  eight bytes must follow the final block; ISIZE must equal the produced size mod
 //            2^32.  Comparing the CRC-32 is the caller's, as is the text of an error.
+// The blocks are a function of their own (decode_blocks), shared with the reader of a zlib stream
+// (RFC 1950: decode_zlib_stream, for the streams of blosc frames in zh_blosc_streams.h):
+//   header   two bytes: CM 8, CINFO <= 7, (CMF << 8 | FLG) % 31 == 0, FDICT clear;
+//   trailer  four bytes, big-endian: the Adler-32 of the content (adler32 computes it across
+//            the lanes; comparing is the caller's).  A zlib stream carries no size: the caller
+//            knows it.
 //
 // Every step returns a Verdict: kOk, or the reason for rejecting the member.
 //
@@ -33,6 +39,7 @@
 //     void     match(d, o, off, n)   d[o+k] = d[o-off + k % off]  (off <= o; only bytes below o
 //                                    are read)
 //     void     spread(d, v, n)       d[lane()] = v in the lanes below n (n <= W): a literal run
+//     uint32_t sum(v)                the sum of v over the lanes, in every lane (the Adler-32)
 // Control flow is uniform over the lanes except where a loop starts at lane().  Symbols are
 // decoded uniformly: every lane reads the same bit container and the same table entries.
 // Literals are not stored one by one: lane k keeps the k-th literal of a run, and a run is
@@ -72,6 +79,8 @@ enum Verdict : int32_t {
   kTruncated, kNoRoom, kTrailerTruncated, kSizeMismatch,
   // the callers': the checksum, and what the device plan adds
   kCrcMismatch, kNotToTheEnd,
+  // a zlib stream (RFC 1950): its header, its trailer and its checksum
+  kZlibHeader, kZlibDictionary, kZlibTrailerTruncated, kAdlerMismatch,
   kVerdicts
 };
 
@@ -359,19 +368,14 @@ ZH_GD_HD void read_fixed(Work& w) {
   (void)code_build(w.lens + 288, 32, &w.dc, w.dsym, w.next, kDistSet);
 }
 
-// ---- a member ------------------------------------------------------------------------------
-// Decodes the first member of src[0, len) into dst[0, room).  *made: the bytes produced; *used:
-// the member's bytes, its trailer included; *crc: the stored CRC-32.  kTrace (host): one
+// ---- the blocks ----------------------------------------------------------------------------
+// The DEFLATE blocks from in.pos up to and including the final block, into dst[0, room).  *made:
+// the bytes produced.  What stands before the first block and behind the last one is the
+// caller's: decode_member (gzip) and decode_zlib_stream (zlib) below.  kTrace (host): one
 // BlockInfo per block into *tr.
 template <class P, bool kTrace = false>
-ZH_GD_HD Verdict decode_member(const uint8_t* src, size_t len, uint8_t* dst, uint64_t room,
-                               Work& w, P& p, uint64_t* made, size_t* used, uint32_t* crc,
-                               Trace* tr = nullptr) {
-  size_t hsize = 0;
-  Verdict hv = member_header(src, len, &hsize);
-  if (hv) return hv;
-  Bits in;
-  in.init(src + hsize, len - hsize);
+ZH_GD_HD Verdict decode_blocks(Bits& in, uint8_t* dst, uint64_t room, Work& w, P& p,
+                               uint64_t* made, Trace* tr = nullptr) {
   uint64_t out = 0;
   uint32_t run = 0, mine = 0;  // the literal run: `mine` is this lane's
   int tables = 0;              // 1: the fixed codes are in w, 2: a dynamic block's
@@ -471,6 +475,26 @@ ZH_GD_HD Verdict decode_member(const uint8_t* src, size_t len, uint8_t* dst, uin
       tr->n++;
     }
   }
+  *made = out;
+  return kOk;
+}
+
+// ---- a member ------------------------------------------------------------------------------
+// Decodes the first member of src[0, len) into dst[0, room).  *made: the bytes produced; *used:
+// the member's bytes, its trailer included; *crc: the stored CRC-32.  kTrace (host): one
+// BlockInfo per block into *tr.
+template <class P, bool kTrace = false>
+ZH_GD_HD Verdict decode_member(const uint8_t* src, size_t len, uint8_t* dst, uint64_t room,
+                               Work& w, P& p, uint64_t* made, size_t* used, uint32_t* crc,
+                               Trace* tr = nullptr) {
+  size_t hsize = 0;
+  Verdict hv = member_header(src, len, &hsize);
+  if (hv) return hv;
+  Bits in;
+  in.init(src + hsize, len - hsize);
+  uint64_t out = 0;
+  const Verdict bv = decode_blocks<P, kTrace>(in, dst, room, w, p, &out, tr);
+  if (bv) return bv;
   const uint64_t at = (in.pos + 7) >> 3;
   if (in.len - at < 8) return kTrailerTruncated;
   if (rd_le(in.p + at + 4, 4) != (uint32_t)out) return kSizeMismatch;
@@ -478,6 +502,91 @@ ZH_GD_HD Verdict decode_member(const uint8_t* src, size_t len, uint8_t* dst, uin
   *made = out;
   *used = hsize + (size_t)at + 8;
   return kOk;
+}
+
+// ---- a zlib stream (RFC 1950) --------------------------------------------------------------
+// The two header bytes: CM 8, CINFO <= 7, (CMF << 8 | FLG) a multiple of 31, no preset
+// dictionary.  *cinfo: the window size the writer declared (7: 32 KiB, what compress2 writes).
+ZH_GD_HD Verdict zlib_header(const uint8_t* s, size_t n, uint32_t* cinfo) {
+  if (n < 2) return kZlibHeader;
+  const uint32_t cmf = s[0], flg = s[1];
+  if ((cmf & 15u) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31u != 0) return kZlibHeader;
+  if (flg & 0x20u) return kZlibDictionary;
+  *cinfo = cmf >> 4;
+  return kOk;
+}
+
+// Decodes the zlib stream at src[0, len) into dst[0, room): the header above, the blocks, and
+// the four bytes of the trailer.  *made: the bytes produced; *used: the stream's bytes, its
+// trailer included (what follows is ignored, as zlib's uncompress ignores it); *adler: the stored
+// Adler-32, big-endian in the stream.  Comparing it (adler32 below) is the caller's, as the
+// CRC-32 of a member is.  A distance is checked against the bytes produced so far and not
+// against the declared window, like a zlib built without strict window checking.
+template <class P>
+ZH_GD_HD Verdict decode_zlib_stream(const uint8_t* src, size_t len, uint8_t* dst, uint64_t room,
+                                    Work& w, P& p, uint64_t* made, size_t* used,
+                                    uint32_t* adler) {
+  uint32_t cinfo = 0;
+  const Verdict hv = zlib_header(src, len, &cinfo);
+  if (hv) return hv;
+  Bits in;
+  in.init(src + 2, len - 2);
+  uint64_t out = 0;
+  const Verdict bv = decode_blocks(in, dst, room, w, p, &out);
+  if (bv) return bv;
+  const uint64_t at = (in.pos + 7) >> 3;
+  if (in.len - at < 4) return kZlibTrailerTruncated;
+  const uint8_t* t = in.p + at;
+  *adler = (uint32_t)t[0] << 24 | (uint32_t)t[1] << 16 | (uint32_t)t[2] << 8 | (uint32_t)t[3];
+  *made = out;
+  *used = 2 + (size_t)at + 4;
+  return kOk;
+}
+
+// Across the lanes: the Adler-32 of d[0, n), the same value in every lane.  With M = 65521,
+// A = 1 + sum d[i] mod M and B = n + sum (n - i) d[i] mod M; the value is B << 16 | A.
+// The bytes go in chunks of at most kAdlerChunk; a chunk of L bytes with s1 = sum d[j] and
+// s2 = sum (L - j) d[j] takes (A, B) to (A + s1, B + L A + s2).  Inside a chunk lane l takes
+// the four bytes at j0 = 4 (W r + l) of every round r (bytes past L count as zero), so with
+// s = d0 + d1 + d2 + d3 of a round its share of s2 is
+//     (L - 4 l) sum s  -  4 W sum r s  -  sum (d1 + 2 d2 + 3 d3)
+// in 64-bit sums that cannot overflow: L <= 2^24 gives at most 2^16 rounds in a wave, sum s <
+// 2^26, sum r s < 2^42, and the products stay below 2^51 (on one lane: 2^22 rounds, sum s < 2^32,
+// sum r s < 2^54, products below 2^57).  The share is a sum of non-negative terms, so the
+// differences never wrap.  A lane's two sums are reduced mod M before the lanes are added
+// (P::sum, 32 bits: W values below 2^16).
+// On the device the bytes are what this wave stored: the caller has order() before this.
+constexpr uint32_t kAdlerMod = 65521;
+constexpr uint64_t kAdlerChunk = (uint64_t)1 << 24;  // a multiple of 4 W
+template <class P>
+ZH_GD_HD uint32_t adler32(const uint8_t* d, uint64_t n, P& p) {
+  uint64_t A = 1, B = 0;
+  for (uint64_t c0 = 0; c0 < n; c0 += kAdlerChunk) {
+    const uint8_t* q = d + c0;
+    const uint64_t L = n - c0 < kAdlerChunk ? n - c0 : kAdlerChunk;
+    const uint64_t l4 = 4 * (uint64_t)p.lane();
+    uint64_t a = 0, c = 0, e = 0, r = 0;
+    for (uint64_t j0 = l4; j0 < L; j0 += 4 * (uint64_t)P::W, r++) {
+      uint32_t v = 0;
+      if (j0 + 4 <= L) {
+        __builtin_memcpy(&v, q + j0, 4);  // little-endian on both sides
+      } else {
+        for (uint64_t t = 0; j0 + t < L; t++) v |= (uint32_t)q[j0 + t] << (8 * t);
+      }
+      const uint32_t d0 = v & 255u, d1 = (v >> 8) & 255u, d2 = (v >> 16) & 255u, d3 = v >> 24;
+      const uint64_t s = d0 + d1 + d2 + d3;
+      a += s;
+      c += r * s;
+      e += d1 + 2 * d2 + 3 * d3;
+    }
+    // a lane without bytes in the chunk has a = c = e = 0 (and L < 4 l does no harm)
+    const uint64_t mine = (L - l4) * a - 4 * (uint64_t)P::W * c - e;
+    const uint64_t s1 = p.sum((uint32_t)(a % kAdlerMod));
+    const uint64_t s2 = p.sum((uint32_t)(mine % kAdlerMod));
+    B = (B + (L % kAdlerMod) * A + s2) % kAdlerMod;
+    A = (A + s1) % kAdlerMod;
+  }
+  return (uint32_t)(B << 16 | A);
 }
 
 // ---- host lane policies --------------------------------------------------------------------
@@ -501,6 +610,7 @@ struct SerialLanes {
   void spread(uint8_t* d, uint32_t v, uint32_t n) {
     if (n) d[0] = (uint8_t)v;
   }
+  uint32_t sum(uint32_t v) { return v; }
 };
 // Stores nothing: the size query.
 struct CountLanes : SerialLanes {

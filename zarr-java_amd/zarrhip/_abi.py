@@ -26,6 +26,7 @@ ZH_MALLOC_PLAIN = 0x10
 ZH_OUT_DEVICE = 0x2
 # zh_blosc_batch_plan_ex / zh_blosc_decode_batch_ex / zh_debug_blosc_streams_ex flags
 ZH_BLOSC_ZSTD_DEVICE = 0x1
+ZH_BLOSC_ZLIB_DEVICE = 0x4
 ZH_BLOSC_ENC_ZSTD = 0x1    # zh_blosc_compress_ex / zh_blosc_encode_batch_ex: zstd streams
 # zh_array_read_multi_routed per-slab routes (include/zarrhip.h)
 ZH_ROUTE_DIRECT = 0

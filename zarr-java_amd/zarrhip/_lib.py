@@ -466,7 +466,8 @@ class DeviceContext:
         (address, nbytes) pairs of host memory the caller keeps alive): returns the device
         buffer holding every decoded frame and, per frame, (dst_off, nbytes, where).  The
         caller frees the buffer (self.free).  flags: 0, or A.ZH_BLOSC_ZSTD_DEVICE (frames whose
-        streams are plain zstd frames are decoded on the device too)."""
+        streams are plain zstd frames are decoded on the device too) | A.ZH_BLOSC_ZLIB_DEVICE
+        (the same for frames whose streams are zlib streams)."""
         arr, keep = blosc_frame_array(frames)
         err = C.create_string_buffer(1024)
         total = self.L.zh_blosc_batch_plan_ex(arr, len(frames), int(flags), err, 1024)

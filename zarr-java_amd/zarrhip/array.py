@@ -47,6 +47,12 @@ BLOSC_DEVICE_DEFAULT = "1"
 # the batch call, as before.  The default follows the measurement in DESIGN.md ("Blosc zstd
 # streams on the device").
 BLOSC_ZSTD_DEVICE_DEFAULT = "0"
+# ZH_BLOSC_ZLIB_DEVICE: on the same route, "1" passes ZH_BLOSC_ZLIB_DEVICE to the batch, so frames
+# whose streams are zlib streams with compress2's header (c-blosc's for cname zlib) are inflated
+# on the device as well; "0" passes no flag and such frames are decoded by zh_blosc_decompress
+# inside the batch call, as before.  The measurement is in DESIGN.md ("Blosc zlib streams on the
+# device").
+BLOSC_ZLIB_DEVICE_DEFAULT = "0"
 # ZH_ZSTD_DEVICE: the same for chains whose only host byte-to-byte stage is zstd
 # (zh_zstd_decode_batch).  "0": the host route; "2": every eligible read goes to the device;
 # "1" (the default): the rule of DESIGN.md ("Zstd frames on the device"), a read goes to the
@@ -663,9 +669,13 @@ class Array:
 
     @staticmethod
     def _blosc_decode_batch(dev):
-        """DeviceContext.blosc_decode_batch with the flags of ZH_BLOSC_ZSTD_DEVICE."""
-        on = os.environ.get("ZH_BLOSC_ZSTD_DEVICE", BLOSC_ZSTD_DEVICE_DEFAULT) != "0"
-        flags = A.ZH_BLOSC_ZSTD_DEVICE if on else 0
+        """DeviceContext.blosc_decode_batch with the flags of ZH_BLOSC_ZSTD_DEVICE and
+        ZH_BLOSC_ZLIB_DEVICE."""
+        flags = 0
+        if os.environ.get("ZH_BLOSC_ZSTD_DEVICE", BLOSC_ZSTD_DEVICE_DEFAULT) != "0":
+            flags |= A.ZH_BLOSC_ZSTD_DEVICE
+        if os.environ.get("ZH_BLOSC_ZLIB_DEVICE", BLOSC_ZLIB_DEVICE_DEFAULT) != "0":
+            flags |= A.ZH_BLOSC_ZLIB_DEVICE
         return lambda frames: dev.blosc_decode_batch(frames, flags=flags)
 
     def _zstd_chain(self):

@@ -273,7 +273,9 @@ class BloscCodec(Codec):
     raises UnsupportedChainError).  Array.read hands the frames of a chain whose only host stage
     is this codec to the device in one batch instead (ZH_BLOSC_DEVICE: LZ4 / BloscLZ / raw
     streams; with ZH_BLOSC_ZSTD_DEVICE=1 also frames whose streams are plain zstd frames, the
-    default cname's; zlib payloads stay with zh_blosc_decompress).  encode compresses cname lz4 / lz4hc with the library's own
+    default cname's; with ZH_BLOSC_ZLIB_DEVICE=1 also frames whose streams are zlib streams as
+    compress2 writes them; without its switch a compressor's payloads stay with
+    zh_blosc_decompress).  encode compresses cname lz4 / lz4hc with the library's own
     LZ4 writer (zh_blosc_compress: byte-identical to the frames Array.write makes on the
     device; clevel is not honoured, and blocks are at most 64 KiB).  With ZH_BLOSC_ZSTD_ENCODE=1
     cname zstd is compressed as well (zh_blosc_compress_ex with ZH_BLOSC_ENC_ZSTD: the LZ4
