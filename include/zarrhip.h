@@ -721,8 +721,27 @@ double zh_debug_blosc_encode_kernel_ms(void);
  * device memory is its raw bytes three and a half times over (scratch: the raw size and 16
  * bytes per stream; records: 1.5 x; the compact frames) and the small tables.  Any other bit →
  * ZH_EINVAL.  zh_blosc_decompress, libzstd on the streams, and zh_blosc_decode_batch_ex with
- * ZH_BLOSC_ZSTD_DEVICE read these frames. */
+ * ZH_BLOSC_ZSTD_DEVICE read these frames.
+ * ZH_BLOSC_ENC_ZLIB: the frame carries compressor code 3 and every stream is one RFC 1950 zlib
+ * stream of its shuffled bytes: 78 01, then what zh_gzip_compress with blocksize 16 KiB puts
+ * between its 10 header bytes and its 8 trailer bytes (one byte-aligned stored or fixed segment
+ * per 16 KiB piece, each with its sync marker, and the final empty fixed block 03 00), then the
+ * Adler-32 of the shuffled bytes, big-endian; a stream whose payload would reach its raw size is
+ * stored raw.  ZH_BLOSC_ENC_DYNAMIC, valid only together with ZH_BLOSC_ENC_ZLIB: a segment may
+ * take the dynamic form, as zh_gzip_enc_params::dynamic = 1 allows.  The batch call writes the
+ * slab's shuffled blocks to device memory once (shuffle kernel, with the Adler-32 of every
+ * stream behind it), runs the gzip writer's match and coding kernels over the 16 KiB pieces
+ * and lays the frames out with the layout kernel; a slab's device memory is its raw bytes four
+ * and a half times over.  zh_blosc_decompress, zlib on the streams, and zh_blosc_decode_batch_ex
+ * with ZH_BLOSC_ZLIB_DEVICE read these frames.  The valid flag words are 0, 1, 4 and 12; the
+ * value of the zlib bit is 4 because 2 and 3 are refused by every release. */
 #define ZH_BLOSC_ENC_ZSTD 1u
+#define ZH_BLOSC_ENC_ZLIB 4u
+#define ZH_BLOSC_ENC_DYNAMIC 8u
+/* Diagnostic: zh_debug_blosc_encode_kernel_ms of the last successful batch with
+ * ZH_BLOSC_ENC_ZLIB, apart: out[0] the shuffle kernel (with the Adler-32), out[1] the match and
+ * coding kernels, out[2] the layout kernel (-1: none yet). */
+void zh_debug_blosc_zlib_encode_parts_ms(double out[3]);
 int zh_blosc_compress_ex(const void* src, size_t n, const zh_blosc_enc_params* params,
                          unsigned flags, void* dst, size_t cap, size_t* cbytes, char* err,
                          size_t errlen);

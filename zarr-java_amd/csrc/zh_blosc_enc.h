@@ -1,8 +1,8 @@
-// zh_blosc_enc.h — the blosc1 frame writer shared by the host and the device: LZ4 streams, or
-// (ZH_BLOSC_ENC_ZSTD) zstd streams.
+// zh_blosc_enc.h — the blosc1 frame writer shared by the host and the device: LZ4 streams,
+// (ZH_BLOSC_ENC_ZSTD) zstd streams or (ZH_BLOSC_ENC_ZLIB) zlib streams.
 //
 // The writer emits what zh_blosc_streams.h reads (build_table is the contract): version 2,
-// versionlz 1, compressor code 1 (LZ4) or 4 (zstd: with_compressor), flags 0x01 byte shuffle /
+// versionlz 1, compressor code 1 (LZ4), 3 (zlib) or 4 (zstd: with_compressor), flags 0x01 byte shuffle /
 // 0x04 bit shuffle (format-2 rule: kShufBit2) / 0x10 blocks not split, the block starts, then per
 // stream an int32 csize and the payload.  This header holds what both sides need, and nothing
 // that needs a device:
@@ -16,13 +16,20 @@
 //     n before writing past out[n - 1]: the caller stores it raw;
 //   * compress_frame: the whole frame on the host with HostLanes (zh_blosc_compress[_ex], the
 //     kernels' byte-for-byte oracle, tools/blosc_enc_check.cpp and blosc_zstd_enc_check.cpp
-//     under sanitizers) over a stream coder: Lz4Coder (encode_stream) or ZstdCoder.
+//     under sanitizers) over a stream coder: Lz4Coder (encode_stream), ZstdCoder or ZlibCoder.
 // Zstd streams (compressor code 4): the layout, the shuffles and the split rule are the LZ4
 // writer's.  A stream's payload is, byte for byte, the frame zh_zstd_compress writes for the
 // shuffled bytes with checksum 0 and block size 64 KiB: the 13-byte header with the 8-byte
 // content size, then one compressed block under its 3-byte header (a stream is at most 64 KiB:
 // always one block), zh_ze::match_block and zh_ze::fse_block behind kZstdHead bytes.  A stream
 // whose kZstdHead + block size would reach its raw size is stored raw (zstd_stream_size).
+// Zlib streams (compressor code 3): again the LZ4 writer's layout.  A stream's payload is one
+// RFC 1950 stream: 78 01 (CM 8, CINFO 7, FLEVEL 0, no dictionary), then what the gzip member
+// writer (zh_gzip_enc.h) puts between its header and its trailer for the shuffled bytes with
+// blocks of zh_gz::kDefaultBlock bytes: one byte-aligned segment per 16 KiB piece (stored or
+// fixed; with ZH_BLOSC_ENC_DYNAMIC the dynamic form is in the choice) and the final empty fixed
+// block 03 00; then the Adler-32 of the shuffled bytes, big-endian.  No match crosses a piece.
+// A stream whose payload would reach its raw size is stored raw (zlib_stream_size).
 // LZ4 end rules (liblz4 decodes the streams): the last 5 bytes are literals, no match starts
 // within the last 12 bytes, a stream shorter than 13 bytes is never encoded, offsets are
 // 1..65535 (a stream is at most 64 KiB).
@@ -32,6 +39,7 @@
 #include <stdint.h>
 
 #include "zh_blosc_streams.h"
+#include "zh_gzip_enc.h"
 #include "zh_lz_match.h"
 #include "zh_zstd_enc.h"
 
@@ -73,7 +81,7 @@ inline int make_layout(size_t n, const zh_blosc_enc_params* p, Layout* L) {
   return ZH_OK;
 }
 
-// The layout with another compressor code in the flags (1 LZ4, 4 zstd).
+// The layout with another compressor code in the flags (1 LZ4, 3 zlib, 4 zstd).
 inline void with_compressor(Layout* L, uint32_t code) {
   L->flags = (L->flags & 0x1Fu) | (code << 5);
 }
@@ -190,6 +198,29 @@ ZH_BS_HD uint32_t zstd_stream_size(uint32_t neb, uint32_t cs) {
   return cs < neb && kZstdHead + cs < neb ? kZstdHead + cs : neb;
 }
 
+// ---- zlib streams ---------------------------------------------------------------------------
+constexpr uint32_t kZlibPiece = zh_gz::kDefaultBlock;  // a stream of 64 KiB is four segments
+// What a stream carries besides its segments: 78 01, 03 00 and the Adler-32.
+constexpr uint32_t kZlibOver = 2 + (uint32_t)zh_gz::kEnding + 4;
+// Room a stream's payload needs beyond its raw size: kZlibOver and the stored segments' headers.
+constexpr uint32_t kZlibHead = kZlibOver + zh_gz::kStoredOver * (kMaxBlock / kZlibPiece);
+ZH_BS_HD uint32_t zlib_pieces(uint32_t neb) { return (neb + kZlibPiece - 1) / kZlibPiece; }
+ZH_BS_HD uint32_t zlib_piece_size(uint32_t neb, uint32_t k) {
+  const uint32_t rest = neb - k * kZlibPiece;
+  return rest < kZlibPiece ? rest : kZlibPiece;
+}
+// Stored size of a stream of neb raw bytes whose segments have `segs` bytes together: neb says
+// the stream is stored raw.
+ZH_BS_HD uint32_t zlib_stream_size(uint32_t neb, uint64_t segs) {
+  return kZlibOver + segs < neb ? kZlibOver + (uint32_t)segs : neb;
+}
+inline void put_zlib_head(uint8_t* d) { d[0] = 0x78, d[1] = 0x01; }
+// 03 00 and the Adler-32, big-endian: zh_gz::kEnding + 4 bytes
+inline void put_zlib_tail(uint8_t* d, uint32_t adler) {
+  zh_gz::put_final(d);
+  for (int i = 0; i < 4; i++) d[zh_gz::kEnding + i] = (uint8_t)(adler >> (8 * (3 - i)));
+}
+
 // ---- stream coders: (stream, neb, out, table) -> stored size, neb: store the stream raw -------
 // kCode: the compressor code of the frame; kHead: room out needs beyond neb bytes.
 struct Lz4Coder {
@@ -219,6 +250,35 @@ struct ZstdCoder {
     const uint32_t h = zh_ze::block_header(cs, 2, true);
     out[13] = (uint8_t)h, out[14] = (uint8_t)(h >> 8), out[15] = (uint8_t)(h >> 16);
     return kZstdHead + cs;
+  }
+};
+
+struct ZlibCoder {
+  static constexpr uint32_t kCode = 3, kHead = kZlibHead;
+  HostLanes w;
+  uint16_t* seq;        // the records of one piece
+  zh_gz::DynWork* dyn;  // ZH_BLOSC_ENC_DYNAMIC, else null
+  explicit ZlibCoder(bool dynamic)
+      : seq(new uint16_t[3 * (kZlibPiece / 4) + 3]), dyn(dynamic ? new zh_gz::DynWork : nullptr) {
+    w.wide = true;
+  }
+  ZlibCoder(const ZlibCoder&) = delete;
+  ~ZlibCoder() {
+    delete dyn;
+    delete[] seq;
+  }
+  uint32_t operator()(const uint8_t* st, uint32_t neb, uint8_t* out, uint32_t* table) {
+    if (neb > kMaxBlock) return neb;
+    uint32_t o = 2;  // a segment is written at out + o only while o + kZlibOver - 2 < neb
+    for (uint32_t k = 0, np = zlib_pieces(neb); k < np; k++) {
+      const uint32_t psz = zlib_piece_size(neb, k);
+      o += zh_gz::put_segment(st + (size_t)k * kZlibPiece, psz, out + o, seq, table, w, dyn);
+      if (zlib_stream_size(neb, o - 2) == neb) return neb;
+    }
+    put_zlib_head(out);
+    zh_gd::SerialLanes one;
+    put_zlib_tail(out + o, zh_gd::adler32(st, neb, one));
+    return o + (uint32_t)zh_gz::kEnding + 4;
   }
 };
 

@@ -1,6 +1,7 @@
 // zh_blosc_enc_kernels.hip — blosc1 frames written on the device, a batch at a time, with LZ4
 // streams (zh_blosc_compress / zh_blosc_encode_bound / zh_blosc_encode_batch) or, with
-// ZH_BLOSC_ENC_ZSTD, zstd streams (zh_blosc_compress_ex / zh_blosc_encode_batch_ex).
+// ZH_BLOSC_ENC_ZSTD, zstd streams, or, with ZH_BLOSC_ENC_ZLIB, zlib streams (zh_blosc_compress_ex /
+// zh_blosc_encode_batch_ex).
 //
 // The raw bytes are in device memory (zh_array_write's chunk buffers); the frames go to the host.
 //   blosc_encode_kernel<CAP>   grid: one workgroup (4 waves) per block of at most CAP bytes (16,
@@ -38,6 +39,23 @@
 //           stream of the block is stored raw (zh_be::zstd_stream_size), the block is loaded
 //           again in its shuffled form and those streams are copied over their regions; a
 //           block without such a stream costs one read of its rows.
+// Zlib streams (ZH_BLOSC_ENC_ZLIB; the format: zh_blosc_enc.h) reuse the gzip writer's kernels:
+//   blosc_shuffle_kernel<CAP>   the same grid and shuffled load, LDS CAP bytes only.  After the
+//           barrier the threads store the shuffled block to its 16-byte aligned region of a
+//           slab-sized buffer in device memory, 16 bytes a thread from LDS, and wave w computes
+//           the Adler-32 (zh_gd::adler32 over the wave) of streams w, w+4, ... from LDS into a
+//           table, one word per stream;
+//   zh::gzip_segments_launch (zh_gzip_enc_kernels.hip)   gzip_match_kernel and gzip_deflate_kernel
+//           (or, with ZH_BLOSC_ENC_DYNAMIC, gzip_deflate_dyn_kernel) over one GBlock row per
+//           16 KiB piece of every stream, the source in the shuffled buffer; the kernel boundary
+//           orders the buffer before them;
+//   host    the segment sizes and the Adler words come back; every size is checked against its
+//           piece, summed per stream, the raw rule applied (zh_be::zlib_stream_size); the jobs:
+//           per stream the csize word and 78 01, each segment from the scratch or 00 LEN NLEN and
+//           the piece from the shuffled buffer, 03 00 and the Adler-32, or the whole stream from
+//           the shuffled buffer.
+// Device memory per slab: the shuffled buffer (the raw size), the segment scratch (the raw size
+// and up to 23 bytes a piece), the records (1.5 x), the compact frames and the small tables.
 // The host checks every size against its stream's raw size, lays out as above (a compressed
 // stream is two jobs: csize word + frame header, block header + block) and gathers.
 // Slabs of at most kSlabBytes of raw input bound the device memory.  LZ4: the scratch (the raw
@@ -56,6 +74,7 @@
 
 #include "zh_blosc_enc.h"
 #include "zh_ctx.h"
+#include "zh_dec_lanes.h"
 #include "zh_enc_device.h"
 
 namespace {
@@ -214,6 +233,31 @@ __global__ __launch_bounds__(kThreads) void blosc_raw_stream_kernel(
   }
 }
 
+// The first phase of the zlib streams: the block in its shuffled form to shuf + b.scratch (the
+// pieces the gzip kernels read, and the streams stored raw), and every stream's Adler-32.
+template <uint32_t CAP>
+__global__ __launch_bounds__(kThreads) void blosc_shuffle_kernel(
+    const EncBlock* __restrict__ blocks, uint8_t* __restrict__ shuf,
+    uint32_t* __restrict__ adlers) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[CAP];
+  const EncBlock b = blocks[blockIdx.x];
+  if (b.size > CAP) return;  // never: the host picks CAP from the block sizes (all threads)
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  load_block(lds, (const uint8_t*)b.src, b, threadIdx.x);
+  __syncthreads();
+  uint8_t* __restrict__ out = shuf + b.scratch;  // 16-byte aligned, up(size, 16) long
+  const uint32_t whole = b.size & ~15u;
+  for (uint32_t q0 = threadIdx.x * 16; q0 < whole; q0 += kThreads * 16)
+    *(uint4*)(out + q0) = *(const uint4*)(lds + q0);
+  for (uint32_t q = whole + threadIdx.x; q < b.size; q += kThreads) out[q] = lds[q];
+  ZdLanes p{lane};
+  const uint32_t neb = b.size / b.nstreams;
+  for (uint32_t s = wave; s < b.nstreams; s += kWaves) {
+    const uint32_t a = zh_gd::adler32(lds + (size_t)s * neb, neb, p);
+    if (lane == 0) adlers[b.first_stream + s] = a;
+  }
+}
+
 template <uint32_t CAP>
 void launch_zstd(hipStream_t s, unsigned nblocks, unsigned nstreams, const EncBlock* blocks,
                  const ZBlock* rows, const zh_ze::Tables* dtab, uint8_t* scratch, uint16_t* seqs,
@@ -227,6 +271,8 @@ void launch_zstd(hipStream_t s, unsigned nblocks, unsigned nstreams, const EncBl
 }
 
 std::atomic<double> g_last_enc_ms{-1.0};
+// the zlib route's kernels apart: shuffle + Adler-32, match + coder, gather (-1: none yet)
+std::atomic<double> g_last_zlib_part[3] = {{-1.0}, {-1.0}, {-1.0}};
 
 struct FramePlan {
   zh_be::Layout L;
@@ -438,6 +484,233 @@ int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, zh_blosc_enc_frame* fram
   return rc;
 }
 
+// encode_slab for zlib streams (ZH_BLOSC_ENC_ZLIB; dynamic: ZH_BLOSC_ENC_DYNAMIC).
+int encode_slab_zlib(zh_ctx* ctx, hipStream_t s, Ring& ring, zh_blosc_enc_frame* frames,
+                     int64_t f0, int64_t f1, const zh_blosc_enc_params* prm, bool dynamic,
+                     uint8_t* dst, int64_t* pos, double* kernel_ms, double* part_ms) {
+  constexpr size_t kStreamMeta = 8;  // per stream: 78 01 | 03 00 and the Adler-32
+  std::vector<FramePlan> plan((size_t)(f1 - f0));
+  std::vector<EncBlock> blocks;
+  std::vector<uint32_t> stream_raw;    // raw size per stream
+  std::vector<uint32_t> stream_row;    // the first row of every stream
+  std::vector<GBlock> rows;            // one per 16 KiB piece of every stream
+  int64_t shuf_total = 0, scratch_total = 0, seq_total = 0, compact_cap = 0, meta_cap = 0,
+          njobs_cap = 0;
+  for (int64_t i = f0; i < f1; i++) {
+    FramePlan& fp = plan[(size_t)(i - f0)];
+    const size_t n = (size_t)frames[i].nbytes;
+    (void)zh_be::make_layout(n, prm, &fp.L);  // validated by the caller
+    zh_be::with_compressor(&fp.L, zh_be::ZlibCoder::kCode);
+    fp.first_block = (int64_t)blocks.size();
+    fp.first_stream = (int64_t)stream_raw.size();
+    fp.raw_only = 4 * (size_t)fp.L.nblocks > n;
+    int64_t frame_jobs = 0;
+    for (uint32_t k = 0; k < fp.L.nblocks && !fp.raw_only; k++) {
+      EncBlock b;
+      b.size = zh_be::block_size(fp.L, n, k);
+      b.nstreams = zh_be::block_streams(fp.L, b.size);
+      b.src = (uint64_t)(uintptr_t)frames[i].src + (uint64_t)k * fp.L.blocksize;
+      b.scratch = (uint64_t)shuf_total;  // the block's region of the shuffled buffer
+      b.typesize = fp.L.typesize, b.shuffle = fp.L.shuffle;
+      b.first_stream = (uint32_t)stream_raw.size();
+      b.pad = 0;
+      const uint32_t neb = b.size / b.nstreams;
+      for (uint32_t q = 0; q < b.nstreams; q++) {
+        stream_raw.push_back(neb);
+        stream_row.push_back((uint32_t)rows.size());
+        const uint32_t np = zh_be::zlib_pieces(neb);
+        for (uint32_t j = 0; j < np; j++) {  // src: an offset here, an address once dmem is known
+          const uint32_t psz = zh_be::zlib_piece_size(neb, j);
+          rows.push_back({(uint64_t)shuf_total + (uint64_t)q * neb + (uint64_t)j * zh_be::kZlibPiece,
+                          (uint64_t)scratch_total, (uint64_t)seq_total, psz, 0});
+          scratch_total += up((int64_t)psz + 8, 16);  // size + 4 bytes, stored as whole words
+          seq_total += up(3 * (int64_t)(psz / 4) + 3, 8);
+        }
+        frame_jobs += 2 + 2 * (int64_t)np;
+      }
+      blocks.push_back(b);
+      shuf_total += up(b.size, 16);
+      if (rows.size() > (size_t)zh::kIntMax) return ZH_EINVAL;
+    }
+    fp.nstreams = (int64_t)stream_raw.size() - fp.first_stream;
+    compact_cap += up((int64_t)n + 16, 16);
+    meta_cap += 16 + (fp.raw_only ? 0 : 4 * (int64_t)fp.L.nblocks) +
+                (int64_t)kStreamMeta * fp.nstreams;
+    njobs_cap += 1 + std::max<int64_t>(frame_jobs, ((int64_t)n + kJobBytes - 1) / kJobBytes);
+  }
+  if (blocks.size() > (size_t)zh::kIntMax || stream_raw.size() > (size_t)zh::kIntMax ||
+      njobs_cap > zh::kIntMax)
+    return ZH_EINVAL;
+  const size_t nst = stream_raw.size(), nrows = rows.size();
+
+  // device memory: [blocks | rows | csizes | adlers | info | jobs | meta | seqs | shuf | scratch |
+  // compact]
+  const size_t o_blocks = 0;
+  const size_t o_rows = (size_t)up((int64_t)(blocks.size() * sizeof(EncBlock)), 256);
+  const size_t o_cs = o_rows + (size_t)up((int64_t)(nrows * sizeof(GBlock)), 256);
+  const size_t o_adler = o_cs + (size_t)up((int64_t)nrows * 4, 256);
+  const size_t o_info = o_adler + (size_t)up((int64_t)nst * 4, 256);
+  const size_t o_jobs = o_info + (size_t)up((int64_t)nrows * 8, 256);
+  const size_t o_meta = o_jobs + (size_t)up(njobs_cap * (int64_t)sizeof(GatherJob), 256);
+  const size_t o_seq = o_meta + (size_t)up(meta_cap, 256);
+  const size_t o_shuf = o_seq + (size_t)up(seq_total * 2, 256);
+  const size_t o_scratch = o_shuf + (size_t)up(shuf_total, 256);
+  const size_t o_compact = o_scratch + (size_t)up(scratch_total, 256);
+  const size_t need = o_compact + (size_t)compact_cap + 256;
+  void* dmem = nullptr;
+  size_t got = 0;
+  if (zh::ctx_alloc(ctx, need, &dmem, &got) != hipSuccess) {
+    (void)hipGetLastError();
+    return ZH_ENOMEM;
+  }
+  uint8_t* d8 = (uint8_t*)dmem;
+  const uint64_t d_shuf = (uint64_t)(uintptr_t)(d8 + o_shuf);
+  for (GBlock& r : rows) r.src += d_shuf;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ev[4]: behind the shuffle
+  for (auto& e : ev) (void)hipEventCreate(&e);
+  const bool timed = ev[0] && ev[1] && ev[2] && ev[3] && ev[4];
+  int rc = ZH_OK;
+  std::vector<uint32_t> cs(nrows, 0), adlers(nst, 0);
+  if (!blocks.empty()) {
+    if (!ring.h2d(d8 + o_blocks, (const uint8_t*)blocks.data(), blocks.size() * sizeof(EncBlock)) ||
+        !ring.h2d(d8 + o_rows, (const uint8_t*)rows.data(), nrows * sizeof(GBlock)))
+      rc = ZH_EHIP;
+    if (rc == ZH_OK) {
+      if (timed) (void)hipEventRecord(ev[0], s);
+      uint32_t cap = 0;
+      for (const EncBlock& b : blocks) cap = std::max(cap, b.size);
+      auto kernel = cap <= (16u << 10)   ? blosc_shuffle_kernel<(16u << 10)>
+                    : cap <= (32u << 10) ? blosc_shuffle_kernel<(32u << 10)>
+                                         : blosc_shuffle_kernel<zh_be::kMaxBlock>;
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks.size()), dim3(kThreads), 0, s,
+                         (const EncBlock*)(d8 + o_blocks), d8 + o_shuf,
+                         (uint32_t*)(d8 + o_adler));
+      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
+      if (timed) (void)hipEventRecord(ev[4], s);
+      if (rc == ZH_OK)
+        rc = zh::gzip_segments_launch(s, d8 + o_rows, (uint32_t)nrows, dynamic, d8 + o_scratch,
+                                      (uint16_t*)(d8 + o_seq), (uint32_t*)(d8 + o_info),
+                                      (uint32_t*)(d8 + o_cs));
+      if (timed) (void)hipEventRecord(ev[1], s);
+    }
+    if (rc == ZH_OK && (!ring.d2h((uint8_t*)cs.data(), d8 + o_cs, nrows * 4) ||
+                        !ring.d2h((uint8_t*)adlers.data(), d8 + o_adler, nst * 4)))
+      rc = ZH_EHIP;
+    // the table lays out device copies: nothing in it may pass its piece's stored size
+    for (size_t k = 0; k < nrows && rc == ZH_OK; k++)
+      if (cs[k] < zh_gz::kMinSegment || cs[k] > rows[k].size + zh_gz::kStoredOver) rc = ZH_EHIP;
+  }
+
+  // layout: the frames side by side in the compact buffer, each 16-byte aligned
+  std::vector<GatherJob> jobs;
+  std::vector<uint8_t> meta;
+  int64_t cpos = 0;
+  if (rc == ZH_OK) {
+    meta.reserve((size_t)meta_cap);
+    jobs.reserve((size_t)njobs_cap);
+    const uint64_t d_meta = (uint64_t)(uintptr_t)(d8 + o_meta);
+    const uint64_t d_scratch = (uint64_t)(uintptr_t)(d8 + o_scratch);
+    const uint64_t d_compact = (uint64_t)(uintptr_t)(d8 + o_compact);
+    std::vector<uint32_t> csz(nst, 0);  // stored size per stream
+    for (size_t k = 0; k < nst; k++) {
+      uint64_t segs = 0;
+      for (uint32_t j = 0, np = zh_be::zlib_pieces(stream_raw[k]); j < np; j++)
+        segs += cs[stream_row[k] + j];
+      csz[k] = zh_be::zlib_stream_size(stream_raw[k], segs);
+    }
+    for (int64_t i = f0; i < f1; i++) {
+      const FramePlan& fp = plan[(size_t)(i - f0)];
+      const zh_be::Layout& L = fp.L;
+      const size_t n = (size_t)frames[i].nbytes;
+      size_t total = 16 + 4 * (size_t)L.nblocks;
+      for (int64_t q = 0; q < fp.nstreams; q++) total += 4 + (size_t)csz[(size_t)(fp.first_stream + q)];
+      const bool memcpyed = n == 0 || fp.raw_only || total > n + 16;
+      const size_t cbytes = memcpyed ? n + 16 : total;
+      const size_t m0 = meta.size();
+      meta.resize(m0 + 16 + (memcpyed ? 0 : 4 * (size_t)L.nblocks));
+      zh_be::put_header(meta.data() + m0, L, memcpyed ? zh_be::memcpyed_flags(L) : L.flags, n,
+                        cbytes);
+      const uint64_t fbase = d_compact + (uint64_t)cpos;
+      jobs.push_back({d_meta + m0, fbase, (uint32_t)(meta.size() - m0), 0, 0, 0});
+      if (memcpyed) {
+        for (size_t o = 0; o < n; o += kJobBytes)
+          jobs.push_back({(uint64_t)(uintptr_t)frames[i].src + o, fbase + 16 + o,
+                          (uint32_t)std::min<size_t>(kJobBytes, n - o), 0, 0, 0});
+      } else {
+        size_t p = 16 + 4 * (size_t)L.nblocks;
+        for (uint32_t k = 0; k < L.nblocks; k++) {
+          const EncBlock& b = blocks[(size_t)fp.first_block + k];
+          zh_be::wr32(meta.data() + m0 + 16 + 4 * (size_t)k, (uint32_t)p);
+          const uint32_t neb = b.size / b.nstreams;
+          for (uint32_t q = 0; q < b.nstreams; q++) {
+            const uint32_t st = b.first_stream + q, c = csz[st];
+            if (c == neb) {  // the stream raw, from the shuffled buffer
+              jobs.push_back({d_shuf + b.scratch + (uint64_t)q * neb, fbase + p, c, c, 4, 0});
+              p += 4 + (size_t)c;
+              continue;
+            }
+            const size_t sm = meta.size();
+            meta.resize(sm + kStreamMeta);
+            zh_be::put_zlib_head(meta.data() + sm);
+            zh_be::put_zlib_tail(meta.data() + sm + 2, adlers[st]);
+            uint64_t d = fbase + p;
+            jobs.push_back({d_meta + sm, d, 2, c, 4, 0});
+            d += 4 + 2;
+            for (uint32_t j = 0, np = zh_be::zlib_pieces(neb); j < np; j++) {
+              const GBlock& r = rows[stream_row[st] + j];
+              const uint32_t size = cs[stream_row[st] + j];
+              if (size == r.size + zh_gz::kStoredOver) {  // 00, then LEN NLEN and the bytes
+                jobs.push_back({d_meta + sm, d, 0, 0, 1, 0});
+                jobs.push_back({r.src, d + 1, r.size, zh_gz::stored_word(r.size), 4, 0});
+              } else {
+                jobs.push_back({d_scratch + r.out, d, size, 0, 0, 0});
+              }
+              d += size;
+            }
+            jobs.push_back({d_meta + sm + 2, d, (uint32_t)zh_gz::kEnding + 4, 0, 0, 0});
+            d += zh_gz::kEnding + 4;
+            if (d - (fbase + p) != 4 + (uint64_t)c) rc = ZH_EHIP;  // layout and size disagree
+            p += 4 + (size_t)c;
+          }
+        }
+      }
+      frames[i].dst_off = *pos + cpos;
+      frames[i].cbytes = (int64_t)cbytes;
+      frames[i].status = ZH_OK;
+      cpos += up((int64_t)cbytes, 16);
+    }
+    if ((int64_t)jobs.size() > njobs_cap || (int64_t)meta.size() > meta_cap || cpos > compact_cap)
+      rc = ZH_EHIP;  // the bounds above are the allocation
+  }
+  if (rc == ZH_OK && !jobs.empty()) {
+    if (!ring.h2d(d8 + o_jobs, (const uint8_t*)jobs.data(), jobs.size() * sizeof(GatherJob)) ||
+        !ring.h2d(d8 + o_meta, meta.data(), meta.size()))
+      rc = ZH_EHIP;
+    if (rc == ZH_OK) {
+      if (timed) (void)hipEventRecord(ev[2], s);
+      hipLaunchKernelGGL(blosc_gather_kernel, dim3((unsigned)jobs.size()), dim3(kThreads), 0, s,
+                         (const GatherJob*)(d8 + o_jobs));
+      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
+      if (timed) (void)hipEventRecord(ev[3], s);
+    }
+    if (rc == ZH_OK && !ring.d2h(dst + *pos, d8 + o_compact, (size_t)cpos)) rc = ZH_EHIP;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
+  if (rc == ZH_OK && timed && !jobs.empty()) {
+    float a = 0, b = 0, c = 0;
+    if (!blocks.empty() && hipEventElapsedTime(&a, ev[0], ev[4]) != hipSuccess) a = 0;
+    if (!blocks.empty() && hipEventElapsedTime(&c, ev[4], ev[1]) != hipSuccess) c = 0;
+    if (hipEventElapsedTime(&b, ev[2], ev[3]) != hipSuccess) b = 0;
+    *kernel_ms += (double)a + (double)c + (double)b;
+    part_ms[0] += (double)a, part_ms[1] += (double)c, part_ms[2] += (double)b;
+  }
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  zh::ctx_release(ctx, dmem, got);
+  if (rc == ZH_OK) *pos += cpos;
+  return rc;
+}
+
 int64_t bound_of(const zh_blosc_enc_frame* frames, int64_t n, const zh_blosc_enc_params* prm) {
   if (n < 0 || (n > 0 && !frames)) return -(int64_t)ZH_EINVAL;
   int64_t total = 0;
@@ -451,7 +724,14 @@ int64_t bound_of(const zh_blosc_enc_frame* frames, int64_t n, const zh_blosc_enc
   return total;
 }
 
-constexpr const char* kBadFlags = "blosc encode: unknown flag (ZH_BLOSC_ENC_ZSTD is the only one)";
+constexpr const char* kBadFlags =
+    "blosc encode: flags are 0, ZH_BLOSC_ENC_ZSTD, ZH_BLOSC_ENC_ZLIB or ZH_BLOSC_ENC_ZLIB | "
+    "ZH_BLOSC_ENC_DYNAMIC";
+constexpr unsigned kZlibDyn = ZH_BLOSC_ENC_ZLIB | ZH_BLOSC_ENC_DYNAMIC;
+bool flags_ok(unsigned flags) {
+  return flags == 0 || flags == ZH_BLOSC_ENC_ZSTD || flags == ZH_BLOSC_ENC_ZLIB ||
+         flags == kZlibDyn;
+}
 constexpr const char* kBadParams =
     "blosc encode: typesize 1..255, shuffle 0..2, blocksize >= 0, frames of at most 2 GiB";
 
@@ -462,7 +742,7 @@ extern "C" {
 int zh_blosc_compress_ex(const void* src, size_t n, const zh_blosc_enc_params* params,
                          unsigned flags, void* dst, size_t cap, size_t* cbytes, char* err,
                          size_t errlen) {
-  if (flags & ~ZH_BLOSC_ENC_ZSTD) {
+  if (!flags_ok(flags)) {
     put_err(err, errlen, kBadFlags);
     return ZH_EINVAL;
   }
@@ -472,6 +752,10 @@ int zh_blosc_compress_ex(const void* src, size_t n, const zh_blosc_enc_params* p
   try {
     if (flags & ZH_BLOSC_ENC_ZSTD) {
       zh_be::ZstdCoder coder(zh_ze::tables());
+      st = zh_be::compress_frame((const uint8_t*)src, n, params, (uint8_t*)dst, cap, &cb, &msg,
+                                 coder);
+    } else if (flags & ZH_BLOSC_ENC_ZLIB) {
+      zh_be::ZlibCoder coder((flags & ZH_BLOSC_ENC_DYNAMIC) != 0);
       st = zh_be::compress_frame((const uint8_t*)src, n, params, (uint8_t*)dst, cap, &cb, &msg,
                                  coder);
     } else {
@@ -502,6 +786,10 @@ int64_t zh_blosc_encode_bound(const zh_blosc_enc_frame* frames, int64_t n,
 
 double zh_debug_blosc_encode_kernel_ms(void) { return g_last_enc_ms.load(); }
 
+void zh_debug_blosc_zlib_encode_parts_ms(double out[3]) {
+  for (int k = 0; k < 3; k++) out[k] = g_last_zlib_part[k].load();
+}
+
 int zh_blosc_encode_batch(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
                           const zh_blosc_enc_params* params, void* dst, int64_t dstcap,
                           void* stream_v, char* err, size_t errlen) {
@@ -512,7 +800,7 @@ int zh_blosc_encode_batch_ex(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
                              const zh_blosc_enc_params* params, unsigned flags, void* dst,
                              int64_t dstcap, void* stream_v, char* err, size_t errlen) {
   if (!ctx) return ZH_EINVAL;
-  if (flags & ~ZH_BLOSC_ENC_ZSTD) {
+  if (!flags_ok(flags)) {
     for (int64_t i = 0; i < n && frames; i++) frames[i].status = ZH_EINVAL;
     put_err(err, errlen, kBadFlags);
     return ZH_EINVAL;
@@ -535,12 +823,15 @@ int zh_blosc_encode_batch_ex(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
   Ring ring;
   int rc = (flags & ZH_BLOSC_ENC_ZSTD) && !dtab ? ZH_ENOMEM : ring.init(ctx, s);
   int64_t pos = 0;
-  double ms = 0;
+  double ms = 0, part[3] = {0, 0, 0};
   for (int64_t f0 = 0; f0 < n && rc == ZH_OK;) {
     int64_t f1 = f0, raw = 0;
     do raw += frames[f1++].nbytes;
     while (f1 < n && raw + frames[f1].nbytes <= kSlabBytes);
-    rc = encode_slab(ctx, s, ring, frames, f0, f1, params, dtab, (uint8_t*)dst, &pos, &ms);
+    rc = (flags & ZH_BLOSC_ENC_ZLIB)
+             ? encode_slab_zlib(ctx, s, ring, frames, f0, f1, params,
+                                (flags & ZH_BLOSC_ENC_DYNAMIC) != 0, (uint8_t*)dst, &pos, &ms, part)
+             : encode_slab(ctx, s, ring, frames, f0, f1, params, dtab, (uint8_t*)dst, &pos, &ms);
     f0 = f1;
   }
   if (rc != ZH_OK) {
@@ -550,6 +841,8 @@ int zh_blosc_encode_batch_ex(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
     return rc;
   }
   g_last_enc_ms.store(ms);
+  if (flags & ZH_BLOSC_ENC_ZLIB)
+    for (int k = 0; k < 3; k++) g_last_zlib_part[k].store(part[k]);
   return ZH_OK;
 }
 

@@ -276,6 +276,15 @@ int zstd_hash_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint64_t* d_
 // stream s; d_jobs: n x {uint64 address, uint32 nbytes <= 64 KiB, uint32 0} and d_raw[n], both in
 // device memory.  The caller folds the spans of a buffer (zh_gz::crc_append, crc_finish).
 int gzip_crc_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint32_t* d_raw);
+// zh_gzip_enc_kernels.hip: the segments (zh_gzip_enc.h: stored, fixed and, with `dynamic`, dynamic)
+// of n blocks of at most 16 KiB on stream s, the match kernel and then the coding kernel.  d_rows:
+// n x GBlock (zh_enc_device.h: the block's address, the offset of its 16-byte aligned region of
+// size + 8 bytes in d_scratch, the offset of its 3 * (size / 4) + 3 records in d_seqs).
+// d_info[2 n]: the kernels' own; d_csize[n]: every segment's size, size + 5 where it is stored
+// (its region then holds nothing of use).
+int gzip_segments_launch(hipStream_t s, const void* d_rows, uint32_t n, bool dynamic,
+                         uint8_t* d_scratch, uint16_t* d_seqs, uint32_t* d_info,
+                         uint32_t* d_csize);
 // zh_gzip.cpp: the plan of zh_gzip_batch_plan; *total: the destination bytes.
 int gzip_plan(zh_gzip_frame* frames, int64_t n, int64_t* total, char* err, size_t errlen);
 // One region over several contexts (zh_array_read_multi_routed / zh_array_read_pieces_multi).

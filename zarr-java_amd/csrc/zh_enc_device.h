@@ -1,7 +1,7 @@
 // zh_enc_device.h — what the device frame writers share (zh_blosc_enc_kernels.hip,
 // zh_zstd_enc_kernels.hip): the wave form of the lane policy of zh_lz_match.h, the second phase
 // of the zstd block writer (zstd_fse_kernel over ZBlock rows, with the encoding tables in device
-// memory), the gather kernel that lays finished pieces out as compact frames, and the copies
+// memory), the GBlock row of the gzip segment kernels, the gather kernel that lays finished pieces out as compact frames, and the copies
 // through the context's page-locked rings.  Device code: included by .hip files only, each of
 // which gets its own copy (anonymous namespace).
 #pragma once
@@ -141,6 +141,15 @@ struct ZBlock {
   uint64_t src;      // device address of the raw block (the blosc writer: unused)
   uint64_t out;      // offset of the block's region in the scratch buffer
   uint64_t seq;      // offset of the block's records in the list, in uint16
+  uint32_t size, pad;
+};
+
+// One block of the gzip segment writer (zh_gzip_enc.h): a block of a gzip member, or a 16 KiB
+// piece of a stream of a blosc frame whose streams are zlib streams.
+struct GBlock {
+  uint64_t src;  // device address of the raw block
+  uint64_t out;  // offset of the block's region in the scratch buffer
+  uint64_t seq;  // offset of the block's records in the list, in uint16
   uint32_t size, pad;
 };
 

@@ -621,14 +621,24 @@ inline void put_header(uint8_t* d) {
   const uint8_t h[kHeader] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
   for (size_t i = 0; i < kHeader; i++) d[i] = h[i];
 }
+// LEN, NLEN of a stored segment as one little-endian word
+inline uint32_t stored_word(uint32_t len) { return len | ((~len & 0xFFFFu) << 16); }
+// A stored segment: 00, LEN, NLEN, the block's n bytes: n + kStoredOver bytes at d.
+inline void put_stored(uint8_t* d, const uint8_t* s, uint32_t n) {
+  const uint32_t word = stored_word(n);
+  d[0] = 0;
+  for (int i = 0; i < 4; i++) d[1 + i] = (uint8_t)(word >> (8 * i));
+  for (uint32_t q = 0; q < n; q++) d[kStoredOver + q] = s[q];
+}
+// The final empty fixed block that ends the segments: kEnding bytes (the zlib streams of the
+// blosc writer, zh_blosc_enc.h, end with the same two).
+inline void put_final(uint8_t* d) { d[0] = 3, d[1] = 0; }
 // 03 00, CRC-32, ISIZE: kEnding + kTrailer bytes
 inline void put_ending(uint8_t* d, uint32_t crc, size_t n) {
-  d[0] = 3, d[1] = 0;
+  put_final(d);
   for (int i = 0; i < 4; i++) d[2 + i] = (uint8_t)(crc >> (8 * i));
   for (int i = 0; i < 4; i++) d[6 + i] = (uint8_t)((uint64_t)n >> (8 * i));
 }
-// LEN, NLEN of a stored segment as one little-endian word
-inline uint32_t stored_word(uint32_t len) { return len | ((~len & 0xFFFFu) << 16); }
 
 struct Params {
   uint32_t B = kDefaultBlock;
@@ -643,6 +653,20 @@ inline bool read_params(const zh_gzip_enc_params* p, Params* out) {
 // read_params refused the `dynamic` field, not the block size
 inline bool bad_dynamic(const zh_gzip_enc_params* p) {
   return p && p->blocksize >= 0 && p->dynamic != 0 && p->dynamic != 1;
+}
+
+// One block (s, bsz) as its segment at d (room for bsz + kStoredOver bytes) on the host: the
+// records into seq (3 * (bsz / 4) + 3 uint16), the smallest form written, the stored one when
+// no other is smaller.  dyn: the work of the dynamic form, or null (stored and fixed only).
+// Returns the segment's size.
+inline uint32_t put_segment(const uint8_t* s, uint32_t bsz, uint8_t* d, uint16_t* seq,
+                            uint32_t* table, zh_lz::HostLanes& w, DynWork* dyn) {
+  uint32_t covered = 0;
+  const uint32_t ns = match_block(s, bsz, seq, table, w, &covered);
+  const uint32_t size = dyn ? deflate_block_dynamic(s, bsz, seq, ns, covered, d, *dyn)
+                            : deflate_block(s, bsz, seq, ns, covered, d);
+  if (size == bsz + kStoredOver) put_stored(d, s, bsz);
+  return size;
 }
 
 // One member on the host with HostLanes.  dst == nullptr: *len = the bound.
@@ -664,7 +688,6 @@ inline int compress_member(const uint8_t* src, size_t n, const zh_gzip_enc_param
     return ZH_EINVAL;
   }
   const size_t nb = block_count(n, P.B);
-  uint8_t* seg = new uint8_t[P.B + kStoredOver];
   uint16_t* seq = new uint16_t[3 * (size_t)(P.B / 4) + 3];
   uint32_t* table = new uint32_t[zh_lz::kHashSize];
   DynWork* dyn = P.dynamic ? new DynWork : nullptr;
@@ -672,30 +695,13 @@ inline int compress_member(const uint8_t* src, size_t n, const zh_gzip_enc_param
   w.wide = true;
   put_header(dst);
   size_t p = kHeader;
-  for (size_t k = 0; k < nb; k++) {
-    const uint32_t bsz = block_size(n, P.B, k);
-    const uint8_t* s = src + k * P.B;
-    uint32_t covered = 0;
-    const uint32_t ns = match_block(s, bsz, seq, table, w, &covered);
-    const uint32_t size = dyn ? deflate_block_dynamic(s, bsz, seq, ns, covered, seg, *dyn)
-                              : deflate_block(s, bsz, seq, ns, covered, seg);
-    if (size == bsz + kStoredOver) {
-      const uint32_t word = stored_word(bsz);
-      dst[p++] = 0;
-      for (int i = 0; i < 4; i++) dst[p++] = (uint8_t)(word >> (8 * i));
-      for (uint32_t q = 0; q < bsz; q++) dst[p + q] = s[q];
-      p += bsz;
-    } else {
-      for (uint32_t q = 0; q < size; q++) dst[p + q] = seg[q];
-      p += size;
-    }
-  }
+  for (size_t k = 0; k < nb; k++)  // the bound leaves every segment its stored size
+    p += put_segment(src + k * P.B, block_size(n, P.B, k), dst + p, seq, table, w, dyn);
   put_ending(dst + p, crc_finish(crc_raw(0, src, n), n), n);
   p += kEnding + kTrailer;
   delete dyn;
   delete[] table;
   delete[] seq;
-  delete[] seg;
   if (p > bound) {
     *msg = "zh_gzip_compress: layout and bound disagree";
     return ZH_EINVAL;

@@ -34,6 +34,8 @@
 //           uploaded table, fixed segments from the scratch, stored segments from the source
 //           behind their 5 header bytes;
 //   D2H     the compact buffer through the context's page-locked out ring into host memory.
+// zh::gzip_segments_launch runs the match and the coding kernel over rows another writer built:
+// the blosc writer's zlib streams (zh_blosc_enc_kernels.hip), a row per 16 KiB piece.
 // Slabs of at most kSlabBytes of raw input bound the device memory: per slab the scratch (the raw
 // size and up to 23 bytes a block), the records (1.5 x), the compact members and the small tables.
 // Every job and block row is built on the host from validated sizes; the size table is checked
@@ -59,12 +61,6 @@ constexpr uint32_t kPieceWords = kPiece / 4, kPieceStride = kPieceWords + 1;
 static_assert(kSpan == kThreads * kPiece, "one piece per thread");
 constexpr size_t kMetaStride = 32;  // per member: the header at 0, the ending and trailer at 10
 
-struct GBlock {
-  uint64_t src;  // device address of the raw block
-  uint64_t out;  // offset of the block's region in the scratch buffer
-  uint64_t seq;  // offset of the block's records in the list, in uint16
-  uint32_t size, pad;
-};
 struct CrcJob {
   uint64_t src;
   uint32_t len, pad;  // len <= kSpan
@@ -783,6 +779,18 @@ int zh::gzip_crc_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint32_t*
   if (n == 0) return ZH_OK;
   hipLaunchKernelGGL(gzip_crc32_kernel, dim3(n), dim3(kThreads), 0, s, (const ::CrcJob*)d_jobs,
                      zh_gz::xpow8(kPiece), d_raw);
+  return hipGetLastError() == hipSuccess ? ZH_OK : ZH_EHIP;
+}
+
+int zh::gzip_segments_launch(hipStream_t s, const void* d_rows, uint32_t n, bool dynamic,
+                             uint8_t* d_scratch, uint16_t* d_seqs, uint32_t* d_info,
+                             uint32_t* d_csize) {
+  static_assert(sizeof(::GBlock) == 32, "the layout zh_ctx.h describes");
+  if (n == 0) return ZH_OK;
+  zh_gz::Params P;
+  P.dynamic = dynamic;
+  launch_match(P.B, s, (const ::GBlock*)d_rows, n, d_seqs, d_info);
+  launch_deflate(P, s, (const ::GBlock*)d_rows, n, d_scratch, d_seqs, d_info, d_csize);
   return hipGetLastError() == hipSuccess ? ZH_OK : ZH_EHIP;
 }
 

@@ -28,6 +28,8 @@ ZH_OUT_DEVICE = 0x2
 ZH_BLOSC_ZSTD_DEVICE = 0x1
 ZH_BLOSC_ZLIB_DEVICE = 0x4
 ZH_BLOSC_ENC_ZSTD = 0x1    # zh_blosc_compress_ex / zh_blosc_encode_batch_ex: zstd streams
+ZH_BLOSC_ENC_ZLIB = 0x4    # zlib streams of stored and fixed segments
+ZH_BLOSC_ENC_DYNAMIC = 0x8  # with ZH_BLOSC_ENC_ZLIB: dynamic segments too
 # zh_array_read_multi_routed per-slab routes (include/zarrhip.h)
 ZH_ROUTE_DIRECT = 0
 ZH_ROUTE_PEER = 1

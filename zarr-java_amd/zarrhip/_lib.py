@@ -108,6 +108,7 @@ _SIGS = {
     "zh_blosc_encode_batch": (C.c_int, [P, C.POINTER(A.zh_blosc_enc_frame), I64,
                                         C.POINTER(A.zh_blosc_enc_params), P, I64, P, CH, SZ]),
     "zh_debug_blosc_encode_kernel_ms": (C.c_double, []),
+    "zh_debug_blosc_zlib_encode_parts_ms": (None, [C.POINTER(C.c_double)]),
     "zh_blosc_compress_ex": (C.c_int, [P, SZ, C.POINTER(A.zh_blosc_enc_params), C.c_uint, P, SZ,
                                        C.POINTER(SZ), CH, SZ]),
     "zh_blosc_encode_batch_ex": (C.c_int, [P, C.POINTER(A.zh_blosc_enc_frame), I64,
@@ -552,12 +553,13 @@ class DeviceContext:
                 arr[i].host_only = 1
 
     def blosc_encode_batch_raw(self, sources, typesize, shuffle, blocksize=0, stream=None,
-                               take=None, zstd=False, flags=None):
+                               take=None, zstd=False, flags=None, zlib=False, dynamic=False):
         """zh_blosc_encode_bound + zh_blosc_encode_batch over (device address, nbytes) pairs:
         (the host buffer the frames arrived in, [(dst_off, cbytes)] per source).  `take(n)`: a
         uint8 array of n bytes to receive them (default: a fresh one).  zstd: the streams are
-        zstd frames (zh_blosc_encode_batch_ex with ZH_BLOSC_ENC_ZSTD); flags: the flags word of
-        that call as it is."""
+        zstd frames (zh_blosc_encode_batch_ex with ZH_BLOSC_ENC_ZSTD); zlib: zlib streams
+        (ZH_BLOSC_ENC_ZLIB; dynamic: with ZH_BLOSC_ENC_DYNAMIC); flags: the flags word of that
+        call as it is."""
         import numpy as np
         n = len(sources)
         arr = (A.zh_blosc_enc_frame * max(1, n))()
@@ -571,7 +573,7 @@ class DeviceContext:
         out = (take or (lambda k: np.empty(k, np.uint8)))(max(1, bound))
         err = C.create_string_buffer(1024)
         if flags is None:
-            flags = A.ZH_BLOSC_ENC_ZSTD if zstd else 0
+            flags = blosc_enc_flags(zstd, zlib, dynamic)
         if flags == 0:
             st = self.L.zh_blosc_encode_batch(self.h, arr, n, C.byref(prm), P(out.ctypes.data),
                                               bound, P(stream), err, 1024)
@@ -582,11 +584,11 @@ class DeviceContext:
         return out, [(int(arr[i].dst_off), int(arr[i].cbytes)) for i in range(n)]
 
     def blosc_encode_batch(self, sources, typesize, shuffle, blocksize=0, stream=None,
-                           take=None, zstd=False):
-        """The blosc1 frames (LZ4 streams; zstd: zstd streams) of (device address, nbytes)
-        sources as a list of bytes."""
+                           take=None, zstd=False, zlib=False, dynamic=False):
+        """The blosc1 frames (LZ4 streams; zstd: zstd streams; zlib, dynamic: zlib streams) of
+        (device address, nbytes) sources as a list of bytes."""
         out, rows = self.blosc_encode_batch_raw(sources, typesize, shuffle, blocksize, stream,
-                                                take, zstd)
+                                                take, zstd, zlib=zlib, dynamic=dynamic)
         mv = memoryview(out)
         return [bytes(mv[o:o + n]) for o, n in rows]
 
@@ -974,10 +976,27 @@ def gzip_encode_kernel_parts_ms():
     return dict(zip(("match", "coder", "crc", "gather"), (float(v) for v in out)))
 
 
-def blosc_compress(data, typesize, shuffle, blocksize=0, zstd=False, flags=None):
+def blosc_zlib_encode_parts_ms():
+    """zh_debug_blosc_zlib_encode_parts_ms: the kernels of the last zlib batch, apart."""
+    out = (C.c_double * 3)()
+    lib().zh_debug_blosc_zlib_encode_parts_ms(out)
+    return dict(zip(("shuffle", "segments", "gather"), (float(v) for v in out)))
+
+
+def blosc_enc_flags(zstd=False, zlib=False, dynamic=False):
+    """The flags word of zh_blosc_compress_ex / zh_blosc_encode_batch_ex behind the keywords (an
+    invalid combination gives a word the library refuses)."""
+    return ((A.ZH_BLOSC_ENC_ZSTD if zstd else 0) | (A.ZH_BLOSC_ENC_ZLIB if zlib else 0) |
+            (A.ZH_BLOSC_ENC_DYNAMIC if dynamic else 0))
+
+
+def blosc_compress(data, typesize, shuffle, blocksize=0, zstd=False, flags=None, zlib=False,
+                   dynamic=False):
     """zh_blosc_compress (no device): one blosc1 LZ4 frame of `data` (shuffle 0 none, 1 byte,
     2 bit).  zstd: zh_blosc_compress_ex with ZH_BLOSC_ENC_ZSTD, the frame's streams are zstd
-    frames; flags: the flags word of that call as it is."""
+    frames; zlib: with ZH_BLOSC_ENC_ZLIB, zlib streams of stored and fixed segments (dynamic:
+    with ZH_BLOSC_ENC_DYNAMIC, dynamic segments too); flags: the flags word of that call as it
+    is."""
     L = lib()
     data = bytes(data)
     prm = A.zh_blosc_enc_params(int(typesize), int(shuffle), int(blocksize))
@@ -985,7 +1004,7 @@ def blosc_compress(data, typesize, shuffle, blocksize=0, zstd=False, flags=None)
     out = C.create_string_buffer(len(data) + 16)
     n = C.c_size_t()
     if flags is None:
-        flags = A.ZH_BLOSC_ENC_ZSTD if zstd else 0
+        flags = blosc_enc_flags(zstd, zlib, dynamic)
     if flags == 0:
         st = L.zh_blosc_compress(data, len(data), C.byref(prm), out, len(data) + 16, C.byref(n),
                                  err, 1024)

@@ -16,7 +16,7 @@ ZH_GZIP_DEVICE, zh_gzip_decode_batch), and blosc LZ4 and zstd frames, which Arra
 compresses on the device (ZH_BLOSC_ENCODE_DEVICE, zh_blosc_encode_batch; ZH_ZSTD_ENCODE_DEVICE,
 zh_zstd_encode_batch), as it does gzip members when asked to (ZH_GZIP_ENCODE_DEVICE=1, or 2
 for dynamic-Huffman segments as well; zh_gzip_encode_batch) and blosc frames with zstd streams
-(ZH_BLOSC_ZSTD_ENCODE=1; zh_blosc_encode_batch_ex).
+(ZH_BLOSC_ZSTD_ENCODE=1; zh_blosc_encode_batch_ex) or zlib streams (ZH_BLOSC_ZLIB_ENCODE=1 or 2).
 """
 import atexit
 import ctypes as C
@@ -81,6 +81,10 @@ BLOSC_ENCODE_DEVICE_DEFAULT = "1"
 # zh_blosc_encode_batch_ex with ZH_BLOSC_ENC_ZSTD) on the route ZH_BLOSC_ENCODE_DEVICE names;
 # unset, such a chain is stored as MEMCPYED frames.  It is opt-in because it changes stored bytes
 # (DESIGN.md "Blosc zstd frames encoded on the device").
+# ZH_BLOSC_ZLIB_ENCODE (read by BloscCodec; default "0"): the same for cname zlib.  "1": zlib
+# streams of stored and fixed segments (ZH_BLOSC_ENC_ZLIB); "2": dynamic segments as well
+# (ZH_BLOSC_ENC_DYNAMIC); any other value: MEMCPYED frames (DESIGN.md "Blosc frames with zlib
+# streams encoded on the device").
 # ZH_ZSTD_ENCODE_DEVICE: the same for a zstd chain (zh_zstd_encode_batch), and "1" for the same
 # reason (DESIGN.md "Zstd frames encoded on the device").
 ZSTD_ENCODE_DEVICE_DEFAULT = "1"
@@ -978,8 +982,9 @@ class Array:
         (ZH_BLOSC_ENCODE_DEVICE / ZH_ZSTD_ENCODE_DEVICE) is not "0", or, for gzip, whose host
         route is zlib and stores other bytes, ZH_GZIP_ENCODE_DEVICE is "1" or "2" ("2": with
         dynamic-Huffman segments, _gzip_dynamic).  Blosc: its cname is
-        lz4 / lz4hc, or zstd with ZH_BLOSC_ZSTD_ENCODE=1 (the blosc compressors written here;
-        clevel is not honoured, as the level of zstd and gzip is not)."""
+        lz4 / lz4hc, zstd with ZH_BLOSC_ZSTD_ENCODE=1 or zlib with ZH_BLOSC_ZLIB_ENCODE=1 or 2 (the
+        blosc compressors written here; clevel is not honoured, as the level of zstd and gzip is
+        not)."""
         if len(devices()) != 1:
             return None
         bb = self.chain.inner_host_bb if self.chain.chain["sharded"] else self.chain.host_bb
@@ -1009,11 +1014,13 @@ class Array:
         codec = (self.chain.inner_host_bb if sharded else self.chain.host_bb)[0]
         if kind == "blosc":
             ts, shuffle, blocksize = codec.enc_params(self.metadata.data_type.getByteCount())
-            zstd = codec.zstd_enc()
+            flags = codec.enc_flags()
 
             def batch(sources, take):
-                return dev.blosc_encode_batch(sources, ts, shuffle, blocksize, take=take,
-                                              zstd=zstd)
+                out, rows = dev.blosc_encode_batch_raw(sources, ts, shuffle, blocksize,
+                                                       take=take, flags=flags)
+                mv = memoryview(out)
+                return [bytes(mv[o:o + n]) for o, n in rows]
         elif kind == "zstd":
             def batch(sources, take):
                 return dev.zstd_encode_batch(sources, bool(codec.checksum), take=take)

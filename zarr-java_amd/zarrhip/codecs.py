@@ -280,12 +280,16 @@ class BloscCodec(Codec):
     device; clevel is not honoured, and blocks are at most 64 KiB).  With ZH_BLOSC_ZSTD_ENCODE=1
     cname zstd is compressed as well (zh_blosc_compress_ex with ZH_BLOSC_ENC_ZSTD: the LZ4
     writer's layout with compressor code 4, every stream one zstd frame as zh_zstd_compress
-    writes it, or raw); the switch is off by default, since it changes stored bytes.  Every
-    other cname, and zstd with the switch unset, is written as a MEMCPYED frame (no compressor
-    for it here)."""
+    writes it, or raw); the switch is off by default, since it changes stored bytes.  With
+    ZH_BLOSC_ZLIB_ENCODE=1 cname zlib is compressed too (ZH_BLOSC_ENC_ZLIB: compressor code 3,
+    every stream one zlib stream of stored and fixed segments over 16 KiB pieces, or raw), and
+    with "2" its segments may be dynamic (ZH_BLOSC_ENC_DYNAMIC); off by default for the same
+    reason.  Every other cname, and zstd or zlib with its switch unset, is written as a
+    MEMCPYED frame (no compressor for it here)."""
     name, kind = "blosc", "bb"
     SHUFFLE_CODE = {"noshuffle": 0, "shuffle": 1, "bitshuffle": 2}
     ZSTD_ENCODE_DEFAULT = "0"
+    ZLIB_ENCODE_DEFAULT = "0"
 
     def __init__(self, cname="zstd", clevel=5, shuffle="noshuffle", typesize=None, blocksize=0):
         self.cfg = {"typesize": typesize, "cname": cname, "clevel": clevel, "shuffle": shuffle,
@@ -317,9 +321,26 @@ class BloscCodec(Codec):
         return (self.cfg.get("cname") == "zstd" and
                 os.environ.get("ZH_BLOSC_ZSTD_ENCODE", self.ZSTD_ENCODE_DEFAULT) == "1")
 
+    def zlib_enc(self):
+        """cname zlib with ZH_BLOSC_ZLIB_ENCODE=1 or 2: encode writes zlib streams.  The flags
+        of the writer: 0 (no), ZH_BLOSC_ENC_ZLIB, or with "2" ZH_BLOSC_ENC_ZLIB |
+        ZH_BLOSC_ENC_DYNAMIC."""
+        from . import _abi as A
+        if self.cfg.get("cname") != "zlib":
+            return 0
+        mode = os.environ.get("ZH_BLOSC_ZLIB_ENCODE", self.ZLIB_ENCODE_DEFAULT)
+        return {"1": A.ZH_BLOSC_ENC_ZLIB,
+                "2": A.ZH_BLOSC_ENC_ZLIB | A.ZH_BLOSC_ENC_DYNAMIC}.get(mode, 0)
+
+    def enc_flags(self):
+        """The flags word zh_blosc_compress_ex / zh_blosc_encode_batch_ex take for this codec."""
+        from . import _abi as A
+        return A.ZH_BLOSC_ENC_ZSTD if self.zstd_enc() else self.zlib_enc()
+
     def compressed(self):
-        """encode compresses (lz4 / lz4hc, or zstd behind its switch) and is not MEMCPYED."""
-        return self.lz4() or self.zstd_enc()
+        """encode compresses (lz4 / lz4hc, or zstd or zlib behind its switch) and is not
+        MEMCPYED."""
+        return self.lz4() or self.zstd_enc() or bool(self.zlib_enc())
 
     def enc_params(self, default_typesize=1):
         """(typesize, shuffle code, blocksize) as zh_blosc_enc_params takes them."""
@@ -333,7 +354,7 @@ class BloscCodec(Codec):
             from ._lib import ZhError, blosc_compress
             try:
                 return blosc_compress(b, *self.enc_params(default_typesize),
-                                      zstd=self.zstd_enc())
+                                      flags=self.enc_flags())
             except ZhError as e:
                 raise ZarrException(f"Error in encoding blosc: {e}") from None
         ts = self.cfg.get("typesize") or 1
