@@ -46,7 +46,7 @@
 //           the Adler-32 (zh_gd::adler32 over the wave) of streams w, w+4, ... from LDS into a
 //           table, one word per stream;
 //   zh::gzip_segments_launch (zh_gzip_enc_kernels.hip)   gzip_match_kernel and gzip_deflate_kernel
-//           (or, with ZH_BLOSC_ENC_DYNAMIC, gzip_deflate_dyn_kernel) over one GBlock row per
+//           (or, with ZH_BLOSC_ENC_DYNAMIC, gzip_deflate_dyn_kernel) over one EncRow row per
 //           16 KiB piece of every stream, the source in the shuffled buffer; the kernel boundary
 //           orders the buffer before them;
 //   host    the segment sizes and the Adler words come back; every size is checked against its
@@ -54,22 +54,28 @@
 //           per stream the csize word and 78 01, each segment from the scratch or 00 LEN NLEN and
 //           the piece from the shuffled buffer, 03 00 and the Adler-32, or the whole stream from
 //           the shuffled buffer.
-// Device memory per slab: the shuffled buffer (the raw size), the segment scratch (the raw size
-// and up to 23 bytes a piece), the records (1.5 x), the compact frames and the small tables.
-// The host checks every size against its stream's raw size, lays out as above (a compressed
-// stream is two jobs: csize word + frame header, block header + block) and gathers.
+// The host side is one function, encode_slab, over the slab driver of zh_enc_device.h (SlabMem,
+// Marks, slab_end, finish_slab) and a device-side coder named after the host's: Lz4Dev, ZstdDev,
+// ZlibDev.  encode_slab owns the frame format: the plan of the blocks, the caps that size the
+// allocation, the largest block's CAP, and every frame's header, MEMCPYED rule, block starts and
+// place.  A coder owns what one stream is: its rows and sections, its launch, the check of the
+// sizes that come back and the stream's jobs (zstd: a compressed stream is two jobs, csize word +
+// frame header, block header + block).
 // Slabs of at most kSlabBytes of raw input bound the device memory.  LZ4: the scratch (the raw
 // size) and the compact frames (the raw size and 16 bytes per frame).  Zstd: the scratch (the
 // raw size and 16 bytes per stream), the records (6 bytes per 4 raw bytes: 1.5 x), the compact
-// frames, and per stream 36 bytes of tables.
-// Every job and block row is built on the host from validated sizes; the csize table is checked
-// against the stream sizes before it lays anything out.
+// frames, and per stream 36 bytes of tables.  Zlib: the shuffled buffer (the raw size), the
+// segment scratch (the raw size and up to 23 bytes a piece), the records (1.5 x), the compact
+// frames and the small tables.
+// Every job and block row is built on the host from validated sizes; the size tables are checked
+// against the stream sizes before they lay anything out.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "zh_blosc_enc.h"
@@ -79,7 +85,6 @@
 
 namespace {
 
-constexpr int64_t kSlabBytes = (int64_t)128 << 20;
 constexpr uint32_t kJobBytes = 64u << 10;  // a MEMCPYED frame is copied in pieces of this size
 
 struct EncBlock {
@@ -181,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void blosc_encode_kernel(
 // (out, behind the kZstdHead bytes of headers) and records (seq).
 template <uint32_t CAP>
 __global__ __launch_bounds__(kThreads) void blosc_zstd_match_kernel(
-    const EncBlock* __restrict__ blocks, const ZBlock* __restrict__ rows,
+    const EncBlock* __restrict__ blocks, const EncRow* __restrict__ rows,
     uint8_t* __restrict__ scratch, uint16_t* __restrict__ seqs, uint32_t* __restrict__ info) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[CAP];
   __shared__ uint32_t tables[kWaves][zh_be::kHashSize];
@@ -197,7 +202,7 @@ __global__ __launch_bounds__(kThreads) void blosc_zstd_match_kernel(
   const uint32_t neb = b.size / b.nstreams;
   for (uint32_t s = wave; s < b.nstreams; s += kWaves) {
     const uint32_t k = b.first_stream + s;
-    const ZBlock r = rows[k];
+    const EncRow r = rows[k];
     uint32_t nl = 0;
     const uint32_t ns = zh_ze::match_block(lds + (size_t)s * neb, neb, scratch + r.out + 3,
                                            seqs + r.seq, tables[wave], w, &nl);
@@ -212,7 +217,7 @@ __global__ __launch_bounds__(kThreads) void blosc_zstd_match_kernel(
 // The streams the size table stores raw, in their shuffled form, over their regions.
 template <uint32_t CAP>
 __global__ __launch_bounds__(kThreads) void blosc_raw_stream_kernel(
-    const EncBlock* __restrict__ blocks, const ZBlock* __restrict__ rows,
+    const EncBlock* __restrict__ blocks, const EncRow* __restrict__ rows,
     const uint32_t* __restrict__ csize, uint8_t* __restrict__ scratch) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[CAP];
   const EncBlock b = blocks[blockIdx.x];
@@ -258,21 +263,237 @@ __global__ __launch_bounds__(kThreads) void blosc_shuffle_kernel(
   }
 }
 
-template <uint32_t CAP>
-void launch_zstd(hipStream_t s, unsigned nblocks, unsigned nstreams, const EncBlock* blocks,
-                 const ZBlock* rows, const zh_ze::Tables* dtab, uint8_t* scratch, uint16_t* seqs,
-                 uint32_t* info, uint32_t* csize) {
-  hipLaunchKernelGGL(blosc_zstd_match_kernel<CAP>, dim3(nblocks), dim3(kThreads), 0, s, blocks,
-                     rows, scratch, seqs, info);
-  hipLaunchKernelGGL(zstd_fse_kernel, dim3((nstreams + 63) / 64), dim3(64), 0, s, rows, nstreams,
-                     dtab, scratch, (const uint16_t*)seqs, (const uint32_t*)info, csize);
-  hipLaunchKernelGGL(blosc_raw_stream_kernel<CAP>, dim3(nblocks), dim3(kThreads), 0, s, blocks,
-                     rows, (const uint32_t*)csize, scratch);
-}
-
 std::atomic<double> g_last_enc_ms{-1.0};
 // the zlib route's kernels apart: shuffle + Adler-32, match + coder, gather (-1: none yet)
 std::atomic<double> g_last_zlib_part[3] = {{-1.0}, {-1.0}, {-1.0}};
+
+// ---- the device-side coders of encode_slab, named after the host's (zh_blosc_enc.h) ------------
+// A coder is what one stream adds to a slab.  While the frames are planned: begin_block (the
+// block's region, EncBlock::scratch), add_stream (its rows and sizes; returns the gather jobs it
+// may need), end_block, nrows.  Then reserve (its sections of the slab's memory), upload (its
+// rows, once the addresses are known), launch<CAP> (its kernels over the blocks), sizes (its
+// tables back and checked: nothing in them may lay out a copy past its stream; csz[k]: the
+// stored size of stream k) and emit (the gather jobs and meta bytes of one stream of stored size
+// c at dst; false: layout and size disagree).  kCode: the compressor code of the frame;
+// kStreamMeta: meta bytes a stream may need; kMid: the mark between the coder's two timed phases
+// (1: it has one).
+
+struct Lz4Dev {
+  static constexpr uint32_t kCode = zh_be::Lz4Coder::kCode;
+  static constexpr int64_t kStreamMeta = 0;
+  static constexpr int kMid = 1;
+  int64_t scratch_total = 0;
+  size_t o_cs = 0, o_scratch = 0;
+  uint64_t d_scratch = 0;
+
+  uint64_t begin_block() const { return (uint64_t)scratch_total; }
+  int64_t add_stream(uint32_t, uint32_t) { return 1; }
+  void end_block(uint32_t size) { scratch_total += up(size, 16); }
+  size_t nrows() const { return 0; }
+  void reserve(SlabMem& mem, size_t nst) {
+    o_cs = mem.add((int64_t)nst * 4);
+    o_scratch = mem.add(scratch_total);
+  }
+  bool upload(Ring&, const SlabMem& mem) {
+    d_scratch = mem.addr(o_scratch);
+    return true;
+  }
+  template <uint32_t CAP>
+  int launch(hipStream_t s, Marks&, const SlabMem& mem, const EncBlock* blocks, unsigned nblocks) {
+    hipLaunchKernelGGL(blosc_encode_kernel<CAP>, dim3(nblocks), dim3(kThreads), 0, s, blocks,
+                       mem.at(o_scratch), (uint32_t*)mem.at(o_cs));
+    return hipGetLastError() == hipSuccess ? ZH_OK : ZH_EHIP;
+  }
+  int sizes(Ring& ring, const SlabMem& mem, const std::vector<uint32_t>& raw,
+            std::vector<uint32_t>& csz) {
+    if (!ring.d2h((uint8_t*)csz.data(), mem.at(o_cs), csz.size() * 4)) return ZH_EHIP;
+    for (size_t k = 0; k < csz.size(); k++)
+      if (csz[k] == 0 || csz[k] > raw[k]) return ZH_EHIP;
+    return ZH_OK;
+  }
+  bool emit(SlabLayout& L, const EncBlock& b, uint32_t q, uint32_t neb, uint32_t c, uint64_t,
+            uint64_t dst) {
+    L.jobs.push_back({d_scratch + b.scratch + (uint64_t)q * neb, dst, c, c, 4, 0});
+    return true;
+  }
+};
+
+// One row per stream: its block region (out, behind the kZstdHead bytes of headers) and records.
+struct ZstdDev {
+  static constexpr uint32_t kCode = zh_be::ZstdCoder::kCode;
+  static constexpr int64_t kStreamMeta = 0;
+  static constexpr int kMid = 1;
+  const zh_ze::Tables* dtab;  // the encoding tables in device memory
+  std::vector<EncRow> rows;
+  int64_t scratch_total = 0, seq_total = 0;
+  size_t o_cs = 0, o_rows = 0, o_info = 0, o_seq = 0, o_scratch = 0;
+  uint64_t d_scratch = 0;
+
+  uint64_t begin_block() const { return (uint64_t)scratch_total; }
+  int64_t add_stream(uint32_t, uint32_t neb) {  // region: [headers | block], 16-byte aligned
+    rows.push_back({0, (uint64_t)scratch_total + zh_be::kZstdHead, (uint64_t)seq_total, neb, 0});
+    scratch_total += up((int64_t)neb + zh_be::kZstdHead, 16);
+    seq_total += up(3 * (int64_t)(neb / 4) + 3, 8);
+    return 2;
+  }
+  void end_block(uint32_t) {}
+  size_t nrows() const { return rows.size(); }
+  void reserve(SlabMem& mem, size_t nst) {
+    o_cs = mem.add((int64_t)nst * 4);
+    o_rows = mem.add((int64_t)(rows.size() * sizeof(EncRow)));
+    o_info = mem.add((int64_t)rows.size() * 8);
+    o_seq = mem.add(seq_total * 2);
+    o_scratch = mem.add(scratch_total);
+  }
+  bool upload(Ring& ring, const SlabMem& mem) {
+    d_scratch = mem.addr(o_scratch);
+    return ring.h2d(mem.at(o_rows), (const uint8_t*)rows.data(), rows.size() * sizeof(EncRow));
+  }
+  template <uint32_t CAP>
+  int launch(hipStream_t s, Marks&, const SlabMem& mem, const EncBlock* blocks, unsigned nblocks) {
+    const EncRow* d_rows = (const EncRow*)mem.at(o_rows);
+    const unsigned nstreams = (unsigned)rows.size();
+    uint32_t* info = (uint32_t*)mem.at(o_info);
+    uint32_t* csize = (uint32_t*)mem.at(o_cs);
+    hipLaunchKernelGGL(blosc_zstd_match_kernel<CAP>, dim3(nblocks), dim3(kThreads), 0, s, blocks,
+                       d_rows, mem.at(o_scratch), (uint16_t*)mem.at(o_seq), info);
+    hipLaunchKernelGGL(zstd_fse_kernel, dim3((nstreams + 63) / 64), dim3(64), 0, s, d_rows,
+                       nstreams, dtab, mem.at(o_scratch), (const uint16_t*)mem.at(o_seq),
+                       (const uint32_t*)info, csize);
+    hipLaunchKernelGGL(blosc_raw_stream_kernel<CAP>, dim3(nblocks), dim3(kThreads), 0, s, blocks,
+                       d_rows, (const uint32_t*)csize, mem.at(o_scratch));
+    return hipGetLastError() == hipSuccess ? ZH_OK : ZH_EHIP;
+  }
+  // the table holds the sizes of the compressed blocks, the raw size where there is none
+  int sizes(Ring& ring, const SlabMem& mem, const std::vector<uint32_t>& raw,
+            std::vector<uint32_t>& csz) {
+    if (!ring.d2h((uint8_t*)csz.data(), mem.at(o_cs), csz.size() * 4)) return ZH_EHIP;
+    for (size_t k = 0; k < csz.size(); k++) {
+      if (csz[k] == 0 || csz[k] > raw[k]) return ZH_EHIP;
+      csz[k] = zh_be::zstd_stream_size(raw[k], csz[k]);
+    }
+    return ZH_OK;
+  }
+  // the stream's region: a raw stream, or [frame header | room | block]
+  bool emit(SlabLayout& L, const EncBlock& b, uint32_t q, uint32_t neb, uint32_t c, uint64_t,
+            uint64_t dst) {
+    const uint64_t blk = d_scratch + rows[b.first_stream + q].out;
+    const uint64_t reg = blk - zh_be::kZstdHead;
+    if (c == neb) {
+      L.jobs.push_back({reg, dst, c, c, 4, 0});
+    } else {
+      const uint32_t fh = (uint32_t)zh_ze::kFrameHeader, bsz = c - zh_be::kZstdHead;
+      L.jobs.push_back({reg, dst, fh, c, 4, 0});
+      L.jobs.push_back({blk, dst + 4 + fh, bsz, zh_ze::block_header(bsz, 2, true), 3, 0});
+    }
+    return true;
+  }
+};
+
+// One row per 16 KiB piece of every stream, the source in the shuffled buffer (the blocks'
+// regions, EncBlock::scratch); the segments are the gzip writer's (zh::gzip_segments_launch).
+struct ZlibDev {
+  static constexpr uint32_t kCode = zh_be::ZlibCoder::kCode;
+  static constexpr int64_t kStreamMeta = 8;  // 78 01 | 03 00 and the Adler-32
+  static constexpr int kMid = 4;             // behind the shuffle
+  bool dynamic;                              // ZH_BLOSC_ENC_DYNAMIC
+  std::vector<EncRow> rows;
+  std::vector<uint32_t> stream_row;  // the first row of every stream
+  std::vector<uint32_t> seg, adlers;  // as they came back: per row, per stream
+  int64_t shuf_total = 0, scratch_total = 0, seq_total = 0;
+  size_t o_rows = 0, o_cs = 0, o_adler = 0, o_info = 0, o_seq = 0, o_shuf = 0, o_scratch = 0;
+  uint64_t d_shuf = 0, d_scratch = 0;
+
+  uint64_t begin_block() const { return (uint64_t)shuf_total; }
+  int64_t add_stream(uint32_t q, uint32_t neb) {
+    stream_row.push_back((uint32_t)rows.size());
+    const uint32_t np = zh_be::zlib_pieces(neb);
+    for (uint32_t j = 0; j < np; j++) {  // src: an offset here, an address once upload knows it
+      const uint32_t psz = zh_be::zlib_piece_size(neb, j);
+      rows.push_back({(uint64_t)shuf_total + (uint64_t)q * neb + (uint64_t)j * zh_be::kZlibPiece,
+                      (uint64_t)scratch_total, (uint64_t)seq_total, psz, 0});
+      scratch_total += up((int64_t)psz + 8, 16);  // size + 4 bytes, stored as whole words
+      seq_total += up(3 * (int64_t)(psz / 4) + 3, 8);
+    }
+    return 2 + 2 * (int64_t)np;
+  }
+  void end_block(uint32_t size) { shuf_total += up(size, 16); }
+  size_t nrows() const { return rows.size(); }
+  void reserve(SlabMem& mem, size_t nst) {
+    o_rows = mem.add((int64_t)(rows.size() * sizeof(EncRow)));
+    o_cs = mem.add((int64_t)rows.size() * 4);
+    o_adler = mem.add((int64_t)nst * 4);
+    o_info = mem.add((int64_t)rows.size() * 8);
+    o_seq = mem.add(seq_total * 2);
+    o_shuf = mem.add(shuf_total);
+    o_scratch = mem.add(scratch_total);
+  }
+  bool upload(Ring& ring, const SlabMem& mem) {
+    d_shuf = mem.addr(o_shuf), d_scratch = mem.addr(o_scratch);
+    for (EncRow& r : rows) r.src += d_shuf;
+    return ring.h2d(mem.at(o_rows), (const uint8_t*)rows.data(), rows.size() * sizeof(EncRow));
+  }
+  template <uint32_t CAP>
+  int launch(hipStream_t s, Marks& marks, const SlabMem& mem, const EncBlock* blocks,
+             unsigned nblocks) {
+    hipLaunchKernelGGL(blosc_shuffle_kernel<CAP>, dim3(nblocks), dim3(kThreads), 0, s, blocks,
+                       mem.at(o_shuf), (uint32_t*)mem.at(o_adler));
+    const int rc = hipGetLastError() == hipSuccess ? ZH_OK : ZH_EHIP;
+    marks.mark(kMid);
+    if (rc != ZH_OK) return rc;
+    return zh::gzip_segments_launch(s, mem.at(o_rows), (uint32_t)rows.size(), dynamic,
+                                    mem.at(o_scratch), (uint16_t*)mem.at(o_seq),
+                                    (uint32_t*)mem.at(o_info), (uint32_t*)mem.at(o_cs));
+  }
+  // nothing in the segment table may pass its piece's stored size; summed per stream
+  int sizes(Ring& ring, const SlabMem& mem, const std::vector<uint32_t>& raw,
+            std::vector<uint32_t>& csz) {
+    seg.assign(rows.size(), 0), adlers.assign(raw.size(), 0);
+    if (!ring.d2h((uint8_t*)seg.data(), mem.at(o_cs), seg.size() * 4) ||
+        !ring.d2h((uint8_t*)adlers.data(), mem.at(o_adler), adlers.size() * 4))
+      return ZH_EHIP;
+    for (size_t k = 0; k < seg.size(); k++)
+      if (seg[k] < zh_gz::kMinSegment || seg[k] > rows[k].size + zh_gz::kStoredOver) return ZH_EHIP;
+    for (size_t k = 0; k < raw.size(); k++) {
+      uint64_t segs = 0;
+      for (uint32_t j = 0, np = zh_be::zlib_pieces(raw[k]); j < np; j++)
+        segs += seg[stream_row[k] + j];
+      csz[k] = zh_be::zlib_stream_size(raw[k], segs);
+    }
+    return ZH_OK;
+  }
+  // the csize word and 78 01, each segment from the scratch or 00 LEN NLEN and the piece from the
+  // shuffled buffer, 03 00 and the Adler-32; or the whole stream raw from the shuffled buffer
+  bool emit(SlabLayout& L, const EncBlock& b, uint32_t q, uint32_t neb, uint32_t c,
+            uint64_t d_meta, uint64_t dst) {
+    if (c == neb) {
+      L.jobs.push_back({d_shuf + b.scratch + (uint64_t)q * neb, dst, c, c, 4, 0});
+      return true;
+    }
+    const uint32_t st = b.first_stream + q;
+    const size_t sm = L.meta.size();
+    L.meta.resize(sm + (size_t)kStreamMeta);
+    zh_be::put_zlib_head(L.meta.data() + sm);
+    zh_be::put_zlib_tail(L.meta.data() + sm + 2, adlers[st]);
+    uint64_t d = dst;
+    L.jobs.push_back({d_meta + sm, d, 2, c, 4, 0});
+    d += 4 + 2;
+    for (uint32_t j = 0, np = zh_be::zlib_pieces(neb); j < np; j++) {
+      const EncRow& r = rows[stream_row[st] + j];
+      const uint32_t size = seg[stream_row[st] + j];
+      if (size == r.size + zh_gz::kStoredOver) {  // 00, then LEN NLEN and the bytes
+        L.jobs.push_back({d_meta + sm, d, 0, 0, 1, 0});
+        L.jobs.push_back({r.src, d + 1, r.size, zh_gz::stored_word(r.size), 4, 0});
+      } else {
+        L.jobs.push_back({d_scratch + r.out, d, size, 0, 0, 0});
+      }
+      d += size;
+    }
+    L.jobs.push_back({d_meta + sm + 2, d, (uint32_t)zh_gz::kEnding + 4, 0, 0, 0});
+    d += zh_gz::kEnding + 4;
+    return d - dst == 4 + (uint64_t)c;
+  }
+};
 
 struct FramePlan {
   zh_be::Layout L;
@@ -280,227 +501,22 @@ struct FramePlan {
   bool raw_only = false;  // the block starts alone pass the bound: MEMCPYED without a launch
 };
 
-// One slab [f0, f1) of the batch; *pos: the running offset in dst.  dtab: the zstd encoding
-// tables in device memory (zstd streams), or null (LZ4 streams).
+// One slab [f0, f1) of the batch; *pos: the running offset in dst.  The frame format is here
+// (the plan of the blocks, the caps, the layout of every frame); what a stream is, is the coder's.
+// part_ms: the coder's first phase, its second (0: it has one), the gather.
+template <class Coder>
 int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, zh_blosc_enc_frame* frames, int64_t f0,
-                int64_t f1, const zh_blosc_enc_params* prm, const zh_ze::Tables* dtab,
-                uint8_t* dst, int64_t* pos, double* kernel_ms) {
-  const bool zstd = dtab != nullptr;
+                int64_t f1, const zh_blosc_enc_params* prm, Coder coder, uint8_t* dst,
+                int64_t* pos, double* kernel_ms, double* part_ms) {
   std::vector<FramePlan> plan((size_t)(f1 - f0));
   std::vector<EncBlock> blocks;
   std::vector<uint32_t> stream_raw;  // raw size per stream
-  std::vector<ZBlock> zrows;         // zstd: per stream, its block region and records
-  int64_t scratch_total = 0, seq_total = 0, compact_cap = 0, meta_cap = 0, njobs_cap = 0;
+  SlabLayout L;
   for (int64_t i = f0; i < f1; i++) {
     FramePlan& fp = plan[(size_t)(i - f0)];
     const size_t n = (size_t)frames[i].nbytes;
     (void)zh_be::make_layout(n, prm, &fp.L);  // validated by the caller
-    if (zstd) zh_be::with_compressor(&fp.L, zh_be::ZstdCoder::kCode);
-    fp.first_block = (int64_t)blocks.size();
-    fp.first_stream = (int64_t)stream_raw.size();
-    fp.raw_only = 4 * (size_t)fp.L.nblocks > n;
-    for (uint32_t k = 0; k < fp.L.nblocks && !fp.raw_only; k++) {
-      EncBlock b;
-      b.size = zh_be::block_size(fp.L, n, k);
-      b.nstreams = zh_be::block_streams(fp.L, b.size);
-      b.src = (uint64_t)(uintptr_t)frames[i].src + (uint64_t)k * fp.L.blocksize;
-      b.scratch = (uint64_t)scratch_total;
-      b.typesize = fp.L.typesize, b.shuffle = fp.L.shuffle;
-      b.first_stream = (uint32_t)stream_raw.size();
-      b.pad = 0;
-      const uint32_t neb = b.size / b.nstreams;
-      for (uint32_t q = 0; q < b.nstreams; q++) stream_raw.push_back(neb);
-      blocks.push_back(b);
-      if (!zstd) {
-        scratch_total += up(b.size, 16);
-        continue;
-      }
-      for (uint32_t q = 0; q < b.nstreams; q++) {  // region: [headers | block], 16-byte aligned
-        zrows.push_back(
-            {0, (uint64_t)scratch_total + zh_be::kZstdHead, (uint64_t)seq_total, neb, 0});
-        scratch_total += up((int64_t)neb + zh_be::kZstdHead, 16);
-        seq_total += up(3 * (int64_t)(neb / 4) + 3, 8);
-      }
-    }
-    fp.nstreams = (int64_t)stream_raw.size() - fp.first_stream;
-    compact_cap += up((int64_t)n + 16, 16);
-    meta_cap += 16 + (fp.raw_only ? 0 : 4 * (int64_t)fp.L.nblocks);
-    njobs_cap += 1 + std::max<int64_t>((zstd ? 2 : 1) * fp.nstreams,
-                                       ((int64_t)n + kJobBytes - 1) / kJobBytes);
-  }
-  if (blocks.size() > (size_t)zh::kIntMax || stream_raw.size() > (size_t)zh::kIntMax ||
-      njobs_cap > zh::kIntMax)
-    return ZH_EINVAL;
-
-  // device memory: [blocks | csizes | jobs | meta | zrows | info | seqs | scratch | compact]
-  // (zrows, info and seqs: zstd streams only)
-  const size_t o_blocks = 0;
-  const size_t o_cs = (size_t)up((int64_t)(blocks.size() * sizeof(EncBlock)), 256);
-  const size_t o_jobs = o_cs + (size_t)up((int64_t)stream_raw.size() * 4, 256);
-  const size_t o_meta = o_jobs + (size_t)up(njobs_cap * (int64_t)sizeof(GatherJob), 256);
-  const size_t o_zrows = o_meta + (size_t)up(meta_cap, 256);
-  const size_t o_info = o_zrows + (size_t)up((int64_t)(zrows.size() * sizeof(ZBlock)), 256);
-  const size_t o_seq = o_info + (size_t)up((int64_t)zrows.size() * 8, 256);
-  const size_t o_scratch = o_seq + (size_t)up(seq_total * 2, 256);
-  const size_t o_compact = o_scratch + (size_t)up(scratch_total, 256);
-  const size_t need = o_compact + (size_t)compact_cap + 256;
-  void* dmem = nullptr;
-  size_t got = 0;
-  if (zh::ctx_alloc(ctx, need, &dmem, &got) != hipSuccess) {
-    (void)hipGetLastError();
-    return ZH_ENOMEM;
-  }
-  uint8_t* d8 = (uint8_t*)dmem;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (auto& e : ev) (void)hipEventCreate(&e);
-  const bool timed = ev[0] && ev[1] && ev[2] && ev[3];
-  int rc = ZH_OK;
-  std::vector<uint32_t> cs(stream_raw.size(), 0);
-  if (!blocks.empty()) {
-    if (!ring.h2d(d8 + o_blocks, (const uint8_t*)blocks.data(), blocks.size() * sizeof(EncBlock)))
-      rc = ZH_EHIP;
-    if (rc == ZH_OK && zstd &&
-        !ring.h2d(d8 + o_zrows, (const uint8_t*)zrows.data(), zrows.size() * sizeof(ZBlock)))
-      rc = ZH_EHIP;
-    if (rc == ZH_OK) {
-      if (timed) (void)hipEventRecord(ev[0], s);
-      uint32_t cap = 0;
-      for (const EncBlock& b : blocks) cap = std::max(cap, b.size);
-      if (zstd) {
-        auto launch = cap <= (16u << 10)   ? launch_zstd<(16u << 10)>
-                      : cap <= (32u << 10) ? launch_zstd<(32u << 10)>
-                                           : launch_zstd<zh_be::kMaxBlock>;
-        launch(s, (unsigned)blocks.size(), (unsigned)zrows.size(),
-               (const EncBlock*)(d8 + o_blocks), (const ZBlock*)(d8 + o_zrows), dtab,
-               d8 + o_scratch, (uint16_t*)(d8 + o_seq), (uint32_t*)(d8 + o_info),
-               (uint32_t*)(d8 + o_cs));
-      } else {
-        auto kernel = cap <= (16u << 10)   ? blosc_encode_kernel<(16u << 10)>
-                      : cap <= (32u << 10) ? blosc_encode_kernel<(32u << 10)>
-                                           : blosc_encode_kernel<zh_be::kMaxBlock>;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks.size()), dim3(kThreads), 0, s,
-                           (const EncBlock*)(d8 + o_blocks), d8 + o_scratch,
-                           (uint32_t*)(d8 + o_cs));
-      }
-      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
-      if (timed) (void)hipEventRecord(ev[1], s);
-    }
-    if (rc == ZH_OK && !ring.d2h((uint8_t*)cs.data(), d8 + o_cs, cs.size() * 4)) rc = ZH_EHIP;
-    // the table lays out device copies: nothing in it may pass its stream's raw size (zstd: the
-    // table holds the sizes of the compressed blocks, the raw size where there is none)
-    for (size_t k = 0; k < cs.size() && rc == ZH_OK; k++) {
-      if (cs[k] == 0 || cs[k] > stream_raw[k]) rc = ZH_EHIP;
-      if (zstd) cs[k] = zh_be::zstd_stream_size(stream_raw[k], cs[k]);
-    }
-  }
-
-  // layout: the frames side by side in the compact buffer, each 16-byte aligned
-  std::vector<GatherJob> jobs;
-  std::vector<uint8_t> meta;
-  int64_t cpos = 0;
-  if (rc == ZH_OK) {
-    meta.reserve((size_t)meta_cap);
-    jobs.reserve((size_t)njobs_cap);
-    const uint64_t d_meta = (uint64_t)(uintptr_t)(d8 + o_meta);
-    const uint64_t d_scratch = (uint64_t)(uintptr_t)(d8 + o_scratch);
-    const uint64_t d_compact = (uint64_t)(uintptr_t)(d8 + o_compact);
-    for (int64_t i = f0; i < f1; i++) {
-      const FramePlan& fp = plan[(size_t)(i - f0)];
-      const zh_be::Layout& L = fp.L;
-      const size_t n = (size_t)frames[i].nbytes;
-      size_t total = 16 + 4 * (size_t)L.nblocks;
-      for (int64_t q = 0; q < fp.nstreams; q++) total += 4 + (size_t)cs[(size_t)(fp.first_stream + q)];
-      const bool memcpyed = n == 0 || fp.raw_only || total > n + 16;
-      const size_t cbytes = memcpyed ? n + 16 : total;
-      const size_t m0 = meta.size();
-      meta.resize(m0 + 16 + (memcpyed ? 0 : 4 * (size_t)L.nblocks));
-      zh_be::put_header(meta.data() + m0, L, memcpyed ? zh_be::memcpyed_flags(L) : L.flags, n,
-                        cbytes);
-      const uint64_t fbase = d_compact + (uint64_t)cpos;
-      jobs.push_back({d_meta + m0, fbase, (uint32_t)(meta.size() - m0), 0, 0, 0});
-      if (memcpyed) {
-        for (size_t o = 0; o < n; o += kJobBytes)
-          jobs.push_back({(uint64_t)(uintptr_t)frames[i].src + o, fbase + 16 + o,
-                          (uint32_t)std::min<size_t>(kJobBytes, n - o), 0, 0, 0});
-      } else {
-        size_t p = 16 + 4 * (size_t)L.nblocks;
-        for (uint32_t k = 0; k < L.nblocks; k++) {
-          const EncBlock& b = blocks[(size_t)fp.first_block + k];
-          zh_be::wr32(meta.data() + m0 + 16 + 4 * (size_t)k, (uint32_t)p);
-          const uint32_t neb = b.size / b.nstreams;
-          for (uint32_t q = 0; q < b.nstreams; q++) {
-            const uint32_t c = cs[b.first_stream + q];
-            if (!zstd) {
-              jobs.push_back({d_scratch + b.scratch + (uint64_t)q * neb, fbase + p, c, c, 4, 0});
-            } else {
-              // the stream's region: a raw stream, or [frame header | room | block]
-              const uint64_t blk = d_scratch + zrows[b.first_stream + q].out;
-              const uint64_t reg = blk - zh_be::kZstdHead;
-              if (c == neb) {
-                jobs.push_back({reg, fbase + p, c, c, 4, 0});
-              } else {
-                const uint32_t fh = (uint32_t)zh_ze::kFrameHeader, bsz = c - zh_be::kZstdHead;
-                jobs.push_back({reg, fbase + p, fh, c, 4, 0});
-                jobs.push_back({blk, fbase + p + 4 + fh, bsz, zh_ze::block_header(bsz, 2, true),
-                                3, 0});
-              }
-            }
-            p += 4 + (size_t)c;
-          }
-        }
-      }
-      frames[i].dst_off = *pos + cpos;
-      frames[i].cbytes = (int64_t)cbytes;
-      frames[i].status = ZH_OK;
-      cpos += up((int64_t)cbytes, 16);
-    }
-    if ((int64_t)jobs.size() > njobs_cap || (int64_t)meta.size() > meta_cap || cpos > compact_cap)
-      rc = ZH_EHIP;  // the bounds above are the allocation
-  }
-  if (rc == ZH_OK && !jobs.empty()) {
-    if (!ring.h2d(d8 + o_jobs, (const uint8_t*)jobs.data(), jobs.size() * sizeof(GatherJob)) ||
-        !ring.h2d(d8 + o_meta, meta.data(), meta.size()))
-      rc = ZH_EHIP;
-    if (rc == ZH_OK) {
-      if (timed) (void)hipEventRecord(ev[2], s);
-      hipLaunchKernelGGL(blosc_gather_kernel, dim3((unsigned)jobs.size()), dim3(kThreads), 0, s,
-                         (const GatherJob*)(d8 + o_jobs));
-      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
-      if (timed) (void)hipEventRecord(ev[3], s);
-    }
-    if (rc == ZH_OK && !ring.d2h(dst + *pos, d8 + o_compact, (size_t)cpos)) rc = ZH_EHIP;
-  }
-  if (hipStreamSynchronize(s) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
-  if (rc == ZH_OK && timed && !jobs.empty()) {
-    float a = 0, b = 0;
-    if (!blocks.empty() && hipEventElapsedTime(&a, ev[0], ev[1]) != hipSuccess) a = 0;
-    if (hipEventElapsedTime(&b, ev[2], ev[3]) != hipSuccess) b = 0;
-    *kernel_ms += (double)a + (double)b;
-  }
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  zh::ctx_release(ctx, dmem, got);
-  if (rc == ZH_OK) *pos += cpos;
-  return rc;
-}
-
-// encode_slab for zlib streams (ZH_BLOSC_ENC_ZLIB; dynamic: ZH_BLOSC_ENC_DYNAMIC).
-int encode_slab_zlib(zh_ctx* ctx, hipStream_t s, Ring& ring, zh_blosc_enc_frame* frames,
-                     int64_t f0, int64_t f1, const zh_blosc_enc_params* prm, bool dynamic,
-                     uint8_t* dst, int64_t* pos, double* kernel_ms, double* part_ms) {
-  constexpr size_t kStreamMeta = 8;  // per stream: 78 01 | 03 00 and the Adler-32
-  std::vector<FramePlan> plan((size_t)(f1 - f0));
-  std::vector<EncBlock> blocks;
-  std::vector<uint32_t> stream_raw;    // raw size per stream
-  std::vector<uint32_t> stream_row;    // the first row of every stream
-  std::vector<GBlock> rows;            // one per 16 KiB piece of every stream
-  int64_t shuf_total = 0, scratch_total = 0, seq_total = 0, compact_cap = 0, meta_cap = 0,
-          njobs_cap = 0;
-  for (int64_t i = f0; i < f1; i++) {
-    FramePlan& fp = plan[(size_t)(i - f0)];
-    const size_t n = (size_t)frames[i].nbytes;
-    (void)zh_be::make_layout(n, prm, &fp.L);  // validated by the caller
-    zh_be::with_compressor(&fp.L, zh_be::ZlibCoder::kCode);
+    zh_be::with_compressor(&fp.L, Coder::kCode);
     fp.first_block = (int64_t)blocks.size();
     fp.first_stream = (int64_t)stream_raw.size();
     fp.raw_only = 4 * (size_t)fp.L.nblocks > n;
@@ -510,204 +526,107 @@ int encode_slab_zlib(zh_ctx* ctx, hipStream_t s, Ring& ring, zh_blosc_enc_frame*
       b.size = zh_be::block_size(fp.L, n, k);
       b.nstreams = zh_be::block_streams(fp.L, b.size);
       b.src = (uint64_t)(uintptr_t)frames[i].src + (uint64_t)k * fp.L.blocksize;
-      b.scratch = (uint64_t)shuf_total;  // the block's region of the shuffled buffer
+      b.scratch = coder.begin_block();
       b.typesize = fp.L.typesize, b.shuffle = fp.L.shuffle;
       b.first_stream = (uint32_t)stream_raw.size();
       b.pad = 0;
       const uint32_t neb = b.size / b.nstreams;
       for (uint32_t q = 0; q < b.nstreams; q++) {
         stream_raw.push_back(neb);
-        stream_row.push_back((uint32_t)rows.size());
-        const uint32_t np = zh_be::zlib_pieces(neb);
-        for (uint32_t j = 0; j < np; j++) {  // src: an offset here, an address once dmem is known
-          const uint32_t psz = zh_be::zlib_piece_size(neb, j);
-          rows.push_back({(uint64_t)shuf_total + (uint64_t)q * neb + (uint64_t)j * zh_be::kZlibPiece,
-                          (uint64_t)scratch_total, (uint64_t)seq_total, psz, 0});
-          scratch_total += up((int64_t)psz + 8, 16);  // size + 4 bytes, stored as whole words
-          seq_total += up(3 * (int64_t)(psz / 4) + 3, 8);
-        }
-        frame_jobs += 2 + 2 * (int64_t)np;
+        frame_jobs += coder.add_stream(q, neb);
       }
       blocks.push_back(b);
-      shuf_total += up(b.size, 16);
-      if (rows.size() > (size_t)zh::kIntMax) return ZH_EINVAL;
+      coder.end_block(b.size);
     }
     fp.nstreams = (int64_t)stream_raw.size() - fp.first_stream;
-    compact_cap += up((int64_t)n + 16, 16);
-    meta_cap += 16 + (fp.raw_only ? 0 : 4 * (int64_t)fp.L.nblocks) +
-                (int64_t)kStreamMeta * fp.nstreams;
-    njobs_cap += 1 + std::max<int64_t>(frame_jobs, ((int64_t)n + kJobBytes - 1) / kJobBytes);
+    L.compact_cap += up((int64_t)n + 16, 16);
+    L.meta_cap += 16 + (fp.raw_only ? 0 : 4 * (int64_t)fp.L.nblocks) +
+                  Coder::kStreamMeta * fp.nstreams;
+    L.njobs_cap += 1 + std::max<int64_t>(frame_jobs, ((int64_t)n + kJobBytes - 1) / kJobBytes);
   }
   if (blocks.size() > (size_t)zh::kIntMax || stream_raw.size() > (size_t)zh::kIntMax ||
-      njobs_cap > zh::kIntMax)
+      coder.nrows() > (size_t)zh::kIntMax || L.njobs_cap > zh::kIntMax)
     return ZH_EINVAL;
-  const size_t nst = stream_raw.size(), nrows = rows.size();
 
-  // device memory: [blocks | rows | csizes | adlers | info | jobs | meta | seqs | shuf | scratch |
-  // compact]
-  const size_t o_blocks = 0;
-  const size_t o_rows = (size_t)up((int64_t)(blocks.size() * sizeof(EncBlock)), 256);
-  const size_t o_cs = o_rows + (size_t)up((int64_t)(nrows * sizeof(GBlock)), 256);
-  const size_t o_adler = o_cs + (size_t)up((int64_t)nrows * 4, 256);
-  const size_t o_info = o_adler + (size_t)up((int64_t)nst * 4, 256);
-  const size_t o_jobs = o_info + (size_t)up((int64_t)nrows * 8, 256);
-  const size_t o_meta = o_jobs + (size_t)up(njobs_cap * (int64_t)sizeof(GatherJob), 256);
-  const size_t o_seq = o_meta + (size_t)up(meta_cap, 256);
-  const size_t o_shuf = o_seq + (size_t)up(seq_total * 2, 256);
-  const size_t o_scratch = o_shuf + (size_t)up(shuf_total, 256);
-  const size_t o_compact = o_scratch + (size_t)up(scratch_total, 256);
-  const size_t need = o_compact + (size_t)compact_cap + 256;
-  void* dmem = nullptr;
-  size_t got = 0;
-  if (zh::ctx_alloc(ctx, need, &dmem, &got) != hipSuccess) {
-    (void)hipGetLastError();
-    return ZH_ENOMEM;
-  }
-  uint8_t* d8 = (uint8_t*)dmem;
-  const uint64_t d_shuf = (uint64_t)(uintptr_t)(d8 + o_shuf);
-  for (GBlock& r : rows) r.src += d_shuf;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ev[4]: behind the shuffle
-  for (auto& e : ev) (void)hipEventCreate(&e);
-  const bool timed = ev[0] && ev[1] && ev[2] && ev[3] && ev[4];
-  int rc = ZH_OK;
-  std::vector<uint32_t> cs(nrows, 0), adlers(nst, 0);
+  // device memory: [blocks | the coder's sections | jobs | meta | compact]
+  SlabMem mem;
+  const size_t o_blocks = mem.add((int64_t)(blocks.size() * sizeof(EncBlock)));
+  coder.reserve(mem, stream_raw.size());
+  L.o_jobs = mem.add(L.njobs_cap * (int64_t)sizeof(GatherJob));
+  L.o_meta = mem.add(L.meta_cap);
+  L.o_compact = mem.add(L.compact_cap);
+  int rc = mem.alloc(ctx);
+  if (rc != ZH_OK) return rc;
+  Marks marks(s, Coder::kMid == 1 ? 4 : 5);  // 0 the coder's kernels 1, 2 gather 3
+  std::vector<uint32_t> cs(stream_raw.size(), 0);  // stored size per stream
   if (!blocks.empty()) {
-    if (!ring.h2d(d8 + o_blocks, (const uint8_t*)blocks.data(), blocks.size() * sizeof(EncBlock)) ||
-        !ring.h2d(d8 + o_rows, (const uint8_t*)rows.data(), nrows * sizeof(GBlock)))
+    if (!ring.h2d(mem.at(o_blocks), (const uint8_t*)blocks.data(),
+                  blocks.size() * sizeof(EncBlock)) ||
+        !coder.upload(ring, mem))
       rc = ZH_EHIP;
     if (rc == ZH_OK) {
-      if (timed) (void)hipEventRecord(ev[0], s);
+      marks.mark(0);
       uint32_t cap = 0;
       for (const EncBlock& b : blocks) cap = std::max(cap, b.size);
-      auto kernel = cap <= (16u << 10)   ? blosc_shuffle_kernel<(16u << 10)>
-                    : cap <= (32u << 10) ? blosc_shuffle_kernel<(32u << 10)>
-                                         : blosc_shuffle_kernel<zh_be::kMaxBlock>;
-      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks.size()), dim3(kThreads), 0, s,
-                         (const EncBlock*)(d8 + o_blocks), d8 + o_shuf,
-                         (uint32_t*)(d8 + o_adler));
-      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
-      if (timed) (void)hipEventRecord(ev[4], s);
-      if (rc == ZH_OK)
-        rc = zh::gzip_segments_launch(s, d8 + o_rows, (uint32_t)nrows, dynamic, d8 + o_scratch,
-                                      (uint16_t*)(d8 + o_seq), (uint32_t*)(d8 + o_info),
-                                      (uint32_t*)(d8 + o_cs));
-      if (timed) (void)hipEventRecord(ev[1], s);
+      const EncBlock* db = (const EncBlock*)mem.at(o_blocks);
+      const unsigned nb = (unsigned)blocks.size();
+      rc = cap <= (16u << 10)   ? coder.template launch<(16u << 10)>(s, marks, mem, db, nb)
+           : cap <= (32u << 10) ? coder.template launch<(32u << 10)>(s, marks, mem, db, nb)
+                                : coder.template launch<zh_be::kMaxBlock>(s, marks, mem, db, nb);
+      marks.mark(1);
     }
-    if (rc == ZH_OK && (!ring.d2h((uint8_t*)cs.data(), d8 + o_cs, nrows * 4) ||
-                        !ring.d2h((uint8_t*)adlers.data(), d8 + o_adler, nst * 4)))
-      rc = ZH_EHIP;
-    // the table lays out device copies: nothing in it may pass its piece's stored size
-    for (size_t k = 0; k < nrows && rc == ZH_OK; k++)
-      if (cs[k] < zh_gz::kMinSegment || cs[k] > rows[k].size + zh_gz::kStoredOver) rc = ZH_EHIP;
+    if (rc == ZH_OK) rc = coder.sizes(ring, mem, stream_raw, cs);
   }
 
   // layout: the frames side by side in the compact buffer, each 16-byte aligned
-  std::vector<GatherJob> jobs;
-  std::vector<uint8_t> meta;
-  int64_t cpos = 0;
   if (rc == ZH_OK) {
-    meta.reserve((size_t)meta_cap);
-    jobs.reserve((size_t)njobs_cap);
-    const uint64_t d_meta = (uint64_t)(uintptr_t)(d8 + o_meta);
-    const uint64_t d_scratch = (uint64_t)(uintptr_t)(d8 + o_scratch);
-    const uint64_t d_compact = (uint64_t)(uintptr_t)(d8 + o_compact);
-    std::vector<uint32_t> csz(nst, 0);  // stored size per stream
-    for (size_t k = 0; k < nst; k++) {
-      uint64_t segs = 0;
-      for (uint32_t j = 0, np = zh_be::zlib_pieces(stream_raw[k]); j < np; j++)
-        segs += cs[stream_row[k] + j];
-      csz[k] = zh_be::zlib_stream_size(stream_raw[k], segs);
-    }
+    L.meta.reserve((size_t)L.meta_cap);
+    L.jobs.reserve((size_t)L.njobs_cap);
+    const uint64_t d_meta = mem.addr(L.o_meta), d_compact = mem.addr(L.o_compact);
     for (int64_t i = f0; i < f1; i++) {
       const FramePlan& fp = plan[(size_t)(i - f0)];
-      const zh_be::Layout& L = fp.L;
+      const zh_be::Layout& Lf = fp.L;
       const size_t n = (size_t)frames[i].nbytes;
-      size_t total = 16 + 4 * (size_t)L.nblocks;
-      for (int64_t q = 0; q < fp.nstreams; q++) total += 4 + (size_t)csz[(size_t)(fp.first_stream + q)];
+      size_t total = 16 + 4 * (size_t)Lf.nblocks;
+      for (int64_t q = 0; q < fp.nstreams; q++) total += 4 + (size_t)cs[(size_t)(fp.first_stream + q)];
       const bool memcpyed = n == 0 || fp.raw_only || total > n + 16;
       const size_t cbytes = memcpyed ? n + 16 : total;
-      const size_t m0 = meta.size();
-      meta.resize(m0 + 16 + (memcpyed ? 0 : 4 * (size_t)L.nblocks));
-      zh_be::put_header(meta.data() + m0, L, memcpyed ? zh_be::memcpyed_flags(L) : L.flags, n,
+      const size_t m0 = L.meta.size();
+      L.meta.resize(m0 + 16 + (memcpyed ? 0 : 4 * (size_t)Lf.nblocks));
+      zh_be::put_header(L.meta.data() + m0, Lf, memcpyed ? zh_be::memcpyed_flags(Lf) : Lf.flags, n,
                         cbytes);
-      const uint64_t fbase = d_compact + (uint64_t)cpos;
-      jobs.push_back({d_meta + m0, fbase, (uint32_t)(meta.size() - m0), 0, 0, 0});
+      const uint64_t fbase = d_compact + (uint64_t)L.cpos;
+      L.jobs.push_back({d_meta + m0, fbase, (uint32_t)(L.meta.size() - m0), 0, 0, 0});
       if (memcpyed) {
         for (size_t o = 0; o < n; o += kJobBytes)
-          jobs.push_back({(uint64_t)(uintptr_t)frames[i].src + o, fbase + 16 + o,
-                          (uint32_t)std::min<size_t>(kJobBytes, n - o), 0, 0, 0});
+          L.jobs.push_back({(uint64_t)(uintptr_t)frames[i].src + o, fbase + 16 + o,
+                            (uint32_t)std::min<size_t>(kJobBytes, n - o), 0, 0, 0});
       } else {
-        size_t p = 16 + 4 * (size_t)L.nblocks;
-        for (uint32_t k = 0; k < L.nblocks; k++) {
+        size_t p = 16 + 4 * (size_t)Lf.nblocks;
+        for (uint32_t k = 0; k < Lf.nblocks; k++) {
           const EncBlock& b = blocks[(size_t)fp.first_block + k];
-          zh_be::wr32(meta.data() + m0 + 16 + 4 * (size_t)k, (uint32_t)p);
+          zh_be::wr32(L.meta.data() + m0 + 16 + 4 * (size_t)k, (uint32_t)p);
           const uint32_t neb = b.size / b.nstreams;
           for (uint32_t q = 0; q < b.nstreams; q++) {
-            const uint32_t st = b.first_stream + q, c = csz[st];
-            if (c == neb) {  // the stream raw, from the shuffled buffer
-              jobs.push_back({d_shuf + b.scratch + (uint64_t)q * neb, fbase + p, c, c, 4, 0});
-              p += 4 + (size_t)c;
-              continue;
-            }
-            const size_t sm = meta.size();
-            meta.resize(sm + kStreamMeta);
-            zh_be::put_zlib_head(meta.data() + sm);
-            zh_be::put_zlib_tail(meta.data() + sm + 2, adlers[st]);
-            uint64_t d = fbase + p;
-            jobs.push_back({d_meta + sm, d, 2, c, 4, 0});
-            d += 4 + 2;
-            for (uint32_t j = 0, np = zh_be::zlib_pieces(neb); j < np; j++) {
-              const GBlock& r = rows[stream_row[st] + j];
-              const uint32_t size = cs[stream_row[st] + j];
-              if (size == r.size + zh_gz::kStoredOver) {  // 00, then LEN NLEN and the bytes
-                jobs.push_back({d_meta + sm, d, 0, 0, 1, 0});
-                jobs.push_back({r.src, d + 1, r.size, zh_gz::stored_word(r.size), 4, 0});
-              } else {
-                jobs.push_back({d_scratch + r.out, d, size, 0, 0, 0});
-              }
-              d += size;
-            }
-            jobs.push_back({d_meta + sm + 2, d, (uint32_t)zh_gz::kEnding + 4, 0, 0, 0});
-            d += zh_gz::kEnding + 4;
-            if (d - (fbase + p) != 4 + (uint64_t)c) rc = ZH_EHIP;  // layout and size disagree
+            const uint32_t c = cs[b.first_stream + q];
+            if (!coder.emit(L, b, q, neb, c, d_meta, fbase + p)) rc = ZH_EHIP;
             p += 4 + (size_t)c;
           }
         }
       }
-      frames[i].dst_off = *pos + cpos;
+      frames[i].dst_off = *pos + L.cpos;
       frames[i].cbytes = (int64_t)cbytes;
       frames[i].status = ZH_OK;
-      cpos += up((int64_t)cbytes, 16);
+      L.cpos += up((int64_t)cbytes, 16);
     }
-    if ((int64_t)jobs.size() > njobs_cap || (int64_t)meta.size() > meta_cap || cpos > compact_cap)
-      rc = ZH_EHIP;  // the bounds above are the allocation
   }
-  if (rc == ZH_OK && !jobs.empty()) {
-    if (!ring.h2d(d8 + o_jobs, (const uint8_t*)jobs.data(), jobs.size() * sizeof(GatherJob)) ||
-        !ring.h2d(d8 + o_meta, meta.data(), meta.size()))
-      rc = ZH_EHIP;
-    if (rc == ZH_OK) {
-      if (timed) (void)hipEventRecord(ev[2], s);
-      hipLaunchKernelGGL(blosc_gather_kernel, dim3((unsigned)jobs.size()), dim3(kThreads), 0, s,
-                         (const GatherJob*)(d8 + o_jobs));
-      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
-      if (timed) (void)hipEventRecord(ev[3], s);
-    }
-    if (rc == ZH_OK && !ring.d2h(dst + *pos, d8 + o_compact, (size_t)cpos)) rc = ZH_EHIP;
+  double gather_ms = 0;
+  rc = finish_slab(s, ring, mem, marks, 2, rc, L, dst, pos, &gather_ms);
+  if (rc == ZH_OK) {
+    const double a = marks.ms(0, Coder::kMid), c = Coder::kMid == 1 ? 0 : marks.ms(Coder::kMid, 1);
+    *kernel_ms += a + c + gather_ms;
+    part_ms[0] += a, part_ms[1] += c, part_ms[2] += gather_ms;
   }
-  if (hipStreamSynchronize(s) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
-  if (rc == ZH_OK && timed && !jobs.empty()) {
-    float a = 0, b = 0, c = 0;
-    if (!blocks.empty() && hipEventElapsedTime(&a, ev[0], ev[4]) != hipSuccess) a = 0;
-    if (!blocks.empty() && hipEventElapsedTime(&c, ev[4], ev[1]) != hipSuccess) c = 0;
-    if (hipEventElapsedTime(&b, ev[2], ev[3]) != hipSuccess) b = 0;
-    *kernel_ms += (double)a + (double)c + (double)b;
-    part_ms[0] += (double)a, part_ms[1] += (double)c, part_ms[2] += (double)b;
-  }
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  zh::ctx_release(ctx, dmem, got);
-  if (rc == ZH_OK) *pos += cpos;
   return rc;
 }
 
@@ -825,13 +744,14 @@ int zh_blosc_encode_batch_ex(zh_ctx* ctx, zh_blosc_enc_frame* frames, int64_t n,
   int64_t pos = 0;
   double ms = 0, part[3] = {0, 0, 0};
   for (int64_t f0 = 0; f0 < n && rc == ZH_OK;) {
-    int64_t f1 = f0, raw = 0;
-    do raw += frames[f1++].nbytes;
-    while (f1 < n && raw + frames[f1].nbytes <= kSlabBytes);
-    rc = (flags & ZH_BLOSC_ENC_ZLIB)
-             ? encode_slab_zlib(ctx, s, ring, frames, f0, f1, params,
-                                (flags & ZH_BLOSC_ENC_DYNAMIC) != 0, (uint8_t*)dst, &pos, &ms, part)
-             : encode_slab(ctx, s, ring, frames, f0, f1, params, dtab, (uint8_t*)dst, &pos, &ms);
+    const int64_t f1 = slab_end(frames, f0, n);
+    auto slab = [&](auto coder) {
+      return encode_slab(ctx, s, ring, frames, f0, f1, params, std::move(coder), (uint8_t*)dst,
+                         &pos, &ms, part);
+    };
+    rc = (flags & ZH_BLOSC_ENC_ZLIB)   ? slab(ZlibDev{(flags & ZH_BLOSC_ENC_DYNAMIC) != 0})
+         : (flags & ZH_BLOSC_ENC_ZSTD) ? slab(ZstdDev{dtab})
+                                       : slab(Lz4Dev{});
     f0 = f1;
   }
   if (rc != ZH_OK) {

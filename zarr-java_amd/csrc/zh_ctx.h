@@ -278,7 +278,7 @@ int zstd_hash_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint64_t* d_
 int gzip_crc_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint32_t* d_raw);
 // zh_gzip_enc_kernels.hip: the segments (zh_gzip_enc.h: stored, fixed and, with `dynamic`, dynamic)
 // of n blocks of at most 16 KiB on stream s, the match kernel and then the coding kernel.  d_rows:
-// n x GBlock (zh_enc_device.h: the block's address, the offset of its 16-byte aligned region of
+// n x EncRow (zh_enc_device.h: the block's address, the offset of its 16-byte aligned region of
 // size + 8 bytes in d_scratch, the offset of its 3 * (size / 4) + 3 records in d_seqs).
 // d_info[2 n]: the kernels' own; d_csize[n]: every segment's size, size + 5 where it is stored
 // (its region then holds nothing of use).

@@ -1,9 +1,14 @@
 // zh_enc_device.h — what the device frame writers share (zh_blosc_enc_kernels.hip,
-// zh_zstd_enc_kernels.hip): the wave form of the lane policy of zh_lz_match.h, the second phase
-// of the zstd block writer (zstd_fse_kernel over ZBlock rows, with the encoding tables in device
-// memory), the GBlock row of the gzip segment kernels, the gather kernel that lays finished pieces out as compact frames, and the copies
-// through the context's page-locked rings.  Device code: included by .hip files only, each of
-// which gets its own copy (anonymous namespace).
+// zh_zstd_enc_kernels.hip, zh_gzip_enc_kernels.hip).  Device code: the wave form of the lane
+// policy of zh_lz_match.h, the EncRow row of the block kernels, the second phase of the zstd
+// block writer (zstd_fse_kernel, with the encoding tables in device memory) and the gather kernel
+// that lays finished pieces out as compact frames.  Host code, the one driver of a slab: the
+// copies through the context's page-locked rings (Ring), the slab's device memory (SlabMem), its
+// timing marks (Marks), the cutter of a batch into slabs (slab_end) and the tail every writer
+// ends a slab with (finish_slab: caps, upload, gather, download, synchronise).  A writer keeps
+// what is its format: the plan of its rows, its launch, the check of the sizes that come back
+// and the layout of its jobs.  Included by .hip files only, each of which gets its own copy
+// (anonymous namespace).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -135,30 +140,24 @@ __global__ __launch_bounds__(kThreads) void blosc_gather_kernel(
   for (uint32_t q = nv * 16 + t; q < n; q += kThreads) d[q] = s[q];
 }
 
-// One block of the zstd block writer (zh_zstd_enc.h): a block of a zstd frame, or a stream of a
-// blosc frame whose streams are zstd frames.
-struct ZBlock {
-  uint64_t src;      // device address of the raw block (the blosc writer: unused)
-  uint64_t out;      // offset of the block's region in the scratch buffer
-  uint64_t seq;      // offset of the block's records in the list, in uint16
-  uint32_t size, pad;
-};
-
-// One block of the gzip segment writer (zh_gzip_enc.h): a block of a gzip member, or a 16 KiB
-// piece of a stream of a blosc frame whose streams are zlib streams.
-struct GBlock {
+// One row of the block kernels.  The zstd block writer (zh_zstd_enc.h): a block of a zstd frame,
+// or a stream of a blosc frame whose streams are zstd frames (src unused).  The gzip segment
+// writer (zh_gzip_enc.h): a block of a gzip member, or a 16 KiB piece of a stream of a blosc
+// frame whose streams are zlib streams.
+struct EncRow {
   uint64_t src;  // device address of the raw block
   uint64_t out;  // offset of the block's region in the scratch buffer
   uint64_t seq;  // offset of the block's records in the list, in uint16
   uint32_t size, pad;
 };
+static_assert(sizeof(EncRow) == 32, "the layout zh_ctx.h describes");
 
 // One thread per block: zh_ze::fse_block walks the block's records backwards and writes the
 // sequences section behind the literals; the size of the compressed block (or the raw size:
 // store it raw) goes to a table.  The records and literals were written by the kernel before:
 // the kernel boundary orders them.  (The gzip writer includes this header and does not launch it.)
 [[maybe_unused]] __global__ __launch_bounds__(64) void zstd_fse_kernel(
-    const ZBlock* __restrict__ blocks, uint32_t nblocks, const zh_ze::Tables* __restrict__ tg,
+    const EncRow* __restrict__ blocks, uint32_t nblocks, const zh_ze::Tables* __restrict__ tg,
     uint8_t* __restrict__ scratch, const uint16_t* __restrict__ seqs,
     const uint32_t* __restrict__ info, uint32_t* __restrict__ csize) {
   __shared__ zh_ze::Tables T;
@@ -167,7 +166,7 @@ struct GBlock {
   __syncthreads();
   const uint32_t k = blockIdx.x * 64 + threadIdx.x;
   if (k >= nblocks) return;
-  const ZBlock b = blocks[k];
+  const EncRow b = blocks[k];
   csize[k] = zh_ze::fse_block(T, seqs + b.seq, info[2 * k], info[2 * k + 1], scratch + b.out,
                               b.size);
 }
@@ -253,5 +252,115 @@ struct Ring {
     return true;
   }
 };
+
+// Slabs of at most kSlabBytes of raw input bound a batch's device memory.  The end of the slab
+// that begins at frame f0: a larger frame is a slab of its own, the next frame joins only while
+// the raw size stays within the limit.
+constexpr int64_t kSlabBytes = (int64_t)128 << 20;
+template <class Frame>
+int64_t slab_end(const Frame* frames, int64_t f0, int64_t n) {
+  int64_t f1 = f0, raw = 0;
+  do raw += frames[f1++].nbytes;
+  while (f1 < n && raw + frames[f1].nbytes <= kSlabBytes);
+  return f1;
+}
+
+// The device memory of one slab: sections of one zh::ctx_alloc block, each 256-byte aligned, with
+// 256 bytes of slack behind the last; released when the slab ends.
+struct SlabMem {
+  zh_ctx* ctx = nullptr;
+  uint8_t* d8 = nullptr;
+  size_t got = 0, next = 0, end = 0;
+
+  size_t add(int64_t bytes) {  // the section's offset
+    const size_t o = next;
+    end = o + (size_t)bytes;
+    next = o + (size_t)up(bytes, 256);
+    return o;
+  }
+  int alloc(zh_ctx* c) {
+    void* p = nullptr;
+    if (zh::ctx_alloc(c, end + 256, &p, &got) != hipSuccess) {
+      (void)hipGetLastError();
+      return ZH_ENOMEM;
+    }
+    ctx = c, d8 = (uint8_t*)p;
+    return ZH_OK;
+  }
+  ~SlabMem() {
+    if (d8) zh::ctx_release(ctx, d8, got);
+  }
+  uint8_t* at(size_t o) const { return d8 + o; }
+  uint64_t addr(size_t o) const { return (uint64_t)(uintptr_t)(d8 + o); }
+};
+
+// The timing marks of one slab: n events on the stream, or none that count if one is missing.
+struct Marks {
+  static constexpr int kMax = 5;
+  hipStream_t s;
+  int n;
+  hipEvent_t ev[kMax] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool timed = true, set[kMax] = {false, false, false, false, false};
+
+  Marks(hipStream_t st, int count) : s(st), n(count) {
+    for (int i = 0; i < n; i++) {
+      (void)hipEventCreate(&ev[i]);
+      timed = timed && ev[i];
+    }
+  }
+  ~Marks() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  void mark(int i) {
+    if (timed) (void)hipEventRecord(ev[i], s), set[i] = true;
+  }
+  // the time between two marks once the stream has passed them; 0 where there is none to report
+  double ms(int i, int j) const {
+    float t = 0;
+    if (!set[i] || !set[j] || hipEventElapsedTime(&t, ev[i], ev[j]) != hipSuccess) t = 0;
+    return (double)t;
+  }
+};
+
+// What a writer's layout hands to finish_slab: the gather jobs, the bytes they copy from the meta
+// section, the length of the compact buffer, and the caps of the plan that sized those sections.
+struct SlabLayout {
+  int64_t njobs_cap = 0, meta_cap = 0, compact_cap = 0;
+  size_t o_jobs = 0, o_meta = 0, o_compact = 0;
+  std::vector<GatherJob> jobs;
+  std::vector<uint8_t> meta;
+  int64_t cpos = 0;
+};
+
+// The tail of a slab.  rc: what the writer's part came to (the stream is synchronised either
+// way).  The layout is checked against the caps that are the allocation, jobs and meta go up,
+// the gather kernel runs between marks g and g + 1, the compact buffer lands at dst + *pos.
+// *pos advances and *gather_ms grows only on success.
+inline int finish_slab(hipStream_t s, Ring& ring, const SlabMem& mem, Marks& marks, int g, int rc,
+                       const SlabLayout& L, uint8_t* dst, int64_t* pos, double* gather_ms) {
+  if (rc == ZH_OK && ((int64_t)L.jobs.size() > L.njobs_cap ||
+                      (int64_t)L.meta.size() > L.meta_cap || L.cpos > L.compact_cap))
+    rc = ZH_EHIP;
+  if (rc == ZH_OK && !L.jobs.empty()) {
+    if (!ring.h2d(mem.at(L.o_jobs), (const uint8_t*)L.jobs.data(),
+                  L.jobs.size() * sizeof(GatherJob)) ||
+        !ring.h2d(mem.at(L.o_meta), L.meta.data(), L.meta.size()))
+      rc = ZH_EHIP;
+    if (rc == ZH_OK) {
+      marks.mark(g);
+      hipLaunchKernelGGL(blosc_gather_kernel, dim3((unsigned)L.jobs.size()), dim3(kThreads), 0, s,
+                         (const GatherJob*)mem.at(L.o_jobs));
+      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
+      marks.mark(g + 1);
+    }
+    if (rc == ZH_OK && !ring.d2h(dst + *pos, mem.at(L.o_compact), (size_t)L.cpos)) rc = ZH_EHIP;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
+  if (rc != ZH_OK) return rc;
+  *gather_ms += marks.ms(g, g + 1);
+  *pos += L.cpos;
+  return ZH_OK;
+}
 
 }  // namespace

@@ -36,6 +36,8 @@
 //   D2H     the compact buffer through the context's page-locked out ring into host memory.
 // zh::gzip_segments_launch runs the match and the coding kernel over rows another writer built:
 // the blosc writer's zlib streams (zh_blosc_enc_kernels.hip), a row per 16 KiB piece.
+// encode_slab keeps the planning and the layout, which are this format; the slab's memory, marks,
+// cutting and tail (caps, upload, gather, download, synchronise) are the driver of zh_enc_device.h.
 // Slabs of at most kSlabBytes of raw input bound the device memory: per slab the scratch (the raw
 // size and up to 23 bytes a block), the records (1.5 x), the compact members and the small tables.
 // Every job and block row is built on the host from validated sizes; the size table is checked
@@ -54,7 +56,6 @@
 
 namespace {
 
-constexpr int64_t kSlabBytes = (int64_t)128 << 20;
 constexpr uint32_t kSpan = 64u << 10;  // bytes per workgroup of the CRC kernel
 constexpr uint32_t kPiece = 256;       // bytes per thread
 constexpr uint32_t kPieceWords = kPiece / 4, kPieceStride = kPieceWords + 1;
@@ -85,14 +86,14 @@ __device__ inline void load_block(uint8_t* blk, const uint8_t* __restrict__ src,
 
 template <uint32_t CAP, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void gzip_match_kernel(
-    const GBlock* __restrict__ blocks, uint32_t nblocks, uint16_t* __restrict__ seqs,
+    const EncRow* __restrict__ blocks, uint32_t nblocks, uint16_t* __restrict__ seqs,
     uint32_t* __restrict__ info) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[WAVES][CAP];
   __shared__ uint32_t tables[WAVES][zh_lz::kHashSize];
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t k = blockIdx.x * WAVES + wave;
   if (k >= nblocks) return;  // the whole wave: the kernel has no barrier
-  const GBlock b = blocks[k];
+  const EncRow b = blocks[k];
   if (b.size > CAP) return;  // never: the host picks CAP from the block size
   uint8_t* blk = lds[wave];
   load_block(blk, (const uint8_t*)b.src, b.size, lane);
@@ -196,7 +197,7 @@ struct WaveDyn {
 
 template <uint32_t CAP, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void gzip_deflate_kernel(
-    const GBlock* __restrict__ blocks, uint32_t nblocks, uint8_t* __restrict__ scratch,
+    const EncRow* __restrict__ blocks, uint32_t nblocks, uint8_t* __restrict__ scratch,
     const uint16_t* __restrict__ seqs, const uint32_t* __restrict__ info,
     uint32_t* __restrict__ csize) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[WAVES][CAP];
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(WAVES * 64) void gzip_deflate_kernel(
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t k = blockIdx.x * WAVES + wave;
   if (k >= nblocks) return;  // the whole wave: the kernel has no barrier
-  const GBlock b = blocks[k];
+  const EncRow b = blocks[k];
   const uint32_t n = b.size, stored = n + zh_gz::kStoredOver;
   const uint32_t ns = info[2 * k], covered = info[2 * k + 1];
   // the tests of zh_gz::deflate_block before it codes anything, and the list's room
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(WAVES * 64) void gzip_deflate_kernel(
 // first lane's tables and their readers (inside the shared steps).
 template <uint32_t CAP, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void gzip_deflate_dyn_kernel(
-    const GBlock* __restrict__ blocks, uint32_t nblocks, uint8_t* __restrict__ scratch,
+    const EncRow* __restrict__ blocks, uint32_t nblocks, uint8_t* __restrict__ scratch,
     const uint16_t* __restrict__ seqs, const uint32_t* __restrict__ info,
     uint32_t* __restrict__ csize) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[WAVES][CAP];
@@ -306,7 +307,7 @@ __global__ __launch_bounds__(WAVES * 64) void gzip_deflate_dyn_kernel(
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t k = blockIdx.x * WAVES + wave;
   if (k >= nblocks) return;  // the whole wave: the kernel has no barrier
-  const GBlock b = blocks[k];
+  const EncRow b = blocks[k];
   const uint32_t n = b.size, stored = n + zh_gz::kStoredOver;
   const uint32_t ns = info[2 * k], covered = info[2 * k + 1];
   if (n > CAP || ns > n / zh_lz::kMinMatch || covered > n) {
@@ -522,7 +523,7 @@ std::atomic<double> g_last_genc_ms{-1.0};
 std::atomic<double> g_last_genc_part[4] = {{-1.0}, {-1.0}, {-1.0}, {-1.0}};
 enum Part { kMatch = 0, kCoder = 1, kCrc = 2, kGather = 3 };
 
-void launch_match(uint32_t B, hipStream_t s, const GBlock* blocks, uint32_t nblocks,
+void launch_match(uint32_t B, hipStream_t s, const EncRow* blocks, uint32_t nblocks,
                   uint16_t* seqs, uint32_t* info) {
   if (B <= (16u << 10)) {
     hipLaunchKernelGGL((gzip_match_kernel<(16u << 10), 4>), dim3((nblocks + 3) / 4), dim3(256), 0,
@@ -533,7 +534,7 @@ void launch_match(uint32_t B, hipStream_t s, const GBlock* blocks, uint32_t nblo
   }
 }
 
-void launch_deflate(const zh_gz::Params& P, hipStream_t s, const GBlock* blocks,
+void launch_deflate(const zh_gz::Params& P, hipStream_t s, const EncRow* blocks,
                     uint32_t nblocks, uint8_t* scratch, const uint16_t* seqs, const uint32_t* info,
                     uint32_t* csize) {
   const uint32_t B = P.B;
@@ -562,15 +563,16 @@ int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, const uint32_t* crcs,
                 uint8_t* dst, int64_t* pos, double* part_ms) {
   const int64_t nf = f1 - f0;
   std::vector<MemberPlan> plan((size_t)nf);
-  std::vector<GBlock> blocks;
-  int64_t scratch_total = 0, seq_total = 0, compact_cap = 0, njobs_cap = 0;
+  std::vector<EncRow> blocks;
+  SlabLayout L;
+  int64_t scratch_total = 0, seq_total = 0;
   for (int64_t i = f0; i < f1; i++) {
     MemberPlan& mp = plan[(size_t)(i - f0)];
     const size_t n = (size_t)frames[i].nbytes;
     mp.first_block = (int64_t)blocks.size();
     mp.nblocks = (int64_t)zh_gz::block_count(n, P.B);
     for (int64_t k = 0; k < mp.nblocks; k++) {
-      GBlock b;
+      EncRow b;
       b.size = zh_gz::block_size(n, P.B, (size_t)k);
       b.src = (uint64_t)(uintptr_t)frames[i].src + (uint64_t)k * P.B;
       b.out = (uint64_t)scratch_total;
@@ -580,124 +582,92 @@ int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, const uint32_t* crcs,
       scratch_total += up((int64_t)b.size + 8, 16);  // size + 4 bytes, stored as whole words
       seq_total += up(3 * (int64_t)(b.size / 4) + 3, 8);
     }
-    compact_cap += up((int64_t)zh_gz::member_bound(n, P.B), 16);
-    njobs_cap += 2 + 2 * mp.nblocks;
+    L.compact_cap += up((int64_t)zh_gz::member_bound(n, P.B), 16);
+    L.njobs_cap += 2 + 2 * mp.nblocks;
   }
-  if (blocks.size() > (size_t)zh::kIntMax || njobs_cap > zh::kIntMax) return ZH_EINVAL;
+  if (blocks.size() > (size_t)zh::kIntMax || L.njobs_cap > zh::kIntMax) return ZH_EINVAL;
   const size_t nb = blocks.size();
+  L.meta_cap = nf * (int64_t)kMetaStride;
 
   // device memory: [blocks | info | csize | jobs | meta | seqs | scratch | compact]
-  const size_t o_blocks = 0;
-  const size_t o_info = o_blocks + (size_t)up((int64_t)(nb * sizeof(GBlock)), 256);
-  const size_t o_cs = o_info + (size_t)up((int64_t)nb * 8, 256);
-  const size_t o_jobs = o_cs + (size_t)up((int64_t)nb * 4, 256);
-  const size_t o_meta = o_jobs + (size_t)up(njobs_cap * (int64_t)sizeof(GatherJob), 256);
-  const size_t o_seq = o_meta + (size_t)up(nf * (int64_t)kMetaStride, 256);
-  const size_t o_scratch = o_seq + (size_t)up(seq_total * 2, 256);
-  const size_t o_compact = o_scratch + (size_t)up(scratch_total, 256);
-  const size_t need = o_compact + (size_t)compact_cap + 256;
-  void* dmem = nullptr;
-  size_t got = 0;
-  if (zh::ctx_alloc(ctx, need, &dmem, &got) != hipSuccess) {
-    (void)hipGetLastError();
-    return ZH_ENOMEM;
-  }
-  uint8_t* d8 = (uint8_t*)dmem;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (auto& e : ev) (void)hipEventCreate(&e);
-  const bool timed = ev[0] && ev[1] && ev[2] && ev[3] && ev[4];
-  int rc = ZH_OK;
+  SlabMem mem;
+  const size_t o_blocks = mem.add((int64_t)(nb * sizeof(EncRow)));
+  const size_t o_info = mem.add((int64_t)nb * 8);
+  const size_t o_cs = mem.add((int64_t)nb * 4);
+  L.o_jobs = mem.add(L.njobs_cap * (int64_t)sizeof(GatherJob));
+  L.o_meta = mem.add(L.meta_cap);
+  const size_t o_seq = mem.add(seq_total * 2);
+  const size_t o_scratch = mem.add(scratch_total);
+  L.o_compact = mem.add(L.compact_cap);
+  int rc = mem.alloc(ctx);
+  if (rc != ZH_OK) return rc;
+  Marks marks(s, 5);  // 0 match 1 coder 2, 3 gather 4
   std::vector<uint32_t> cs(nb, 0);
-  if (nb && !ring.h2d(d8 + o_blocks, (const uint8_t*)blocks.data(), nb * sizeof(GBlock)))
+  if (nb && !ring.h2d(mem.at(o_blocks), (const uint8_t*)blocks.data(), nb * sizeof(EncRow)))
     rc = ZH_EHIP;
   if (rc == ZH_OK) {
-    if (timed) (void)hipEventRecord(ev[0], s);
+    marks.mark(0);
     if (nb)
-      launch_match(P.B, s, (const GBlock*)(d8 + o_blocks), (uint32_t)nb, (uint16_t*)(d8 + o_seq),
-                   (uint32_t*)(d8 + o_info));
-    if (timed) (void)hipEventRecord(ev[1], s);
+      launch_match(P.B, s, (const EncRow*)mem.at(o_blocks), (uint32_t)nb,
+                   (uint16_t*)mem.at(o_seq), (uint32_t*)mem.at(o_info));
+    marks.mark(1);
     if (nb)
-      launch_deflate(P, s, (const GBlock*)(d8 + o_blocks), (uint32_t)nb, d8 + o_scratch,
-                     (const uint16_t*)(d8 + o_seq), (const uint32_t*)(d8 + o_info),
-                     (uint32_t*)(d8 + o_cs));
+      launch_deflate(P, s, (const EncRow*)mem.at(o_blocks), (uint32_t)nb, mem.at(o_scratch),
+                     (const uint16_t*)mem.at(o_seq), (const uint32_t*)mem.at(o_info),
+                     (uint32_t*)mem.at(o_cs));
     if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
-    if (timed) (void)hipEventRecord(ev[2], s);
+    marks.mark(2);
   }
-  if (rc == ZH_OK && nb && !ring.d2h((uint8_t*)cs.data(), d8 + o_cs, nb * 4)) rc = ZH_EHIP;
+  if (rc == ZH_OK && nb && !ring.d2h((uint8_t*)cs.data(), mem.at(o_cs), nb * 4)) rc = ZH_EHIP;
   // the table lays out device copies: nothing in it may pass its block's stored size
   for (size_t k = 0; k < nb && rc == ZH_OK; k++)
     if (cs[k] < zh_gz::kMinSegment || cs[k] > blocks[k].size + zh_gz::kStoredOver) rc = ZH_EHIP;
 
   // layout: the members side by side in the compact buffer, each 16-byte aligned
-  std::vector<GatherJob> jobs;
-  std::vector<uint8_t> meta;
-  int64_t cpos = 0;
   if (rc == ZH_OK) {
-    meta.resize((size_t)nf * kMetaStride, 0);
-    jobs.reserve((size_t)njobs_cap);
-    const uint64_t d_meta = (uint64_t)(uintptr_t)(d8 + o_meta);
-    const uint64_t d_scratch = (uint64_t)(uintptr_t)(d8 + o_scratch);
-    const uint64_t d_compact = (uint64_t)(uintptr_t)(d8 + o_compact);
+    L.meta.resize((size_t)nf * kMetaStride, 0);
+    L.jobs.reserve((size_t)L.njobs_cap);
+    const uint64_t d_meta = mem.addr(L.o_meta), d_scratch = mem.addr(o_scratch);
+    const uint64_t d_compact = mem.addr(L.o_compact);
     for (int64_t i = f0; i < f1; i++) {
       const MemberPlan& mp = plan[(size_t)(i - f0)];
       const size_t n = (size_t)frames[i].nbytes;
       const size_t m0 = (size_t)(i - f0) * kMetaStride;
-      zh_gz::put_header(meta.data() + m0);
-      zh_gz::put_ending(meta.data() + m0 + zh_gz::kHeader, crcs[i], n);
-      const uint64_t fbase = d_compact + (uint64_t)cpos;
+      zh_gz::put_header(L.meta.data() + m0);
+      zh_gz::put_ending(L.meta.data() + m0 + zh_gz::kHeader, crcs[i], n);
+      const uint64_t fbase = d_compact + (uint64_t)L.cpos;
       uint64_t d = fbase;
-      jobs.push_back({d_meta + m0, d, (uint32_t)zh_gz::kHeader, 0, 0, 0});
+      L.jobs.push_back({d_meta + m0, d, (uint32_t)zh_gz::kHeader, 0, 0, 0});
       d += zh_gz::kHeader;
       for (int64_t k = 0; k < mp.nblocks; k++) {
-        const GBlock& b = blocks[(size_t)(mp.first_block + k)];
+        const EncRow& b = blocks[(size_t)(mp.first_block + k)];
         const uint32_t size = cs[(size_t)(mp.first_block + k)];
         if (size == b.size + zh_gz::kStoredOver) {  // 00, then LEN NLEN and the bytes
-          jobs.push_back({d_meta + m0, d, 0, 0, 1, 0});
-          jobs.push_back({b.src, d + 1, b.size, zh_gz::stored_word(b.size), 4, 0});
+          L.jobs.push_back({d_meta + m0, d, 0, 0, 1, 0});
+          L.jobs.push_back({b.src, d + 1, b.size, zh_gz::stored_word(b.size), 4, 0});
         } else {
-          jobs.push_back({d_scratch + b.out, d, size, 0, 0, 0});
+          L.jobs.push_back({d_scratch + b.out, d, size, 0, 0, 0});
         }
         d += size;
       }
-      jobs.push_back({d_meta + m0 + zh_gz::kHeader, d,
-                      (uint32_t)(zh_gz::kEnding + zh_gz::kTrailer), 0, 0, 0});
+      L.jobs.push_back({d_meta + m0 + zh_gz::kHeader, d,
+                        (uint32_t)(zh_gz::kEnding + zh_gz::kTrailer), 0, 0, 0});
       d += zh_gz::kEnding + zh_gz::kTrailer;
       const size_t total = (size_t)(d - fbase);
       if (total > zh_gz::member_bound(n, P.B)) rc = ZH_EHIP;  // layout and bound disagree
-      frames[i].dst_off = *pos + cpos;
+      frames[i].dst_off = *pos + L.cpos;
       frames[i].cbytes = (int64_t)total;
       frames[i].status = ZH_OK;
-      cpos += up((int64_t)total, 16);
+      L.cpos += up((int64_t)total, 16);
     }
-    if ((int64_t)jobs.size() > njobs_cap || cpos > compact_cap) rc = ZH_EHIP;  // the allocation
   }
-  if (rc == ZH_OK && !jobs.empty()) {
-    if (!ring.h2d(d8 + o_jobs, (const uint8_t*)jobs.data(), jobs.size() * sizeof(GatherJob)) ||
-        !ring.h2d(d8 + o_meta, meta.data(), meta.size()))
-      rc = ZH_EHIP;
-    if (rc == ZH_OK) {
-      if (timed) (void)hipEventRecord(ev[3], s);
-      hipLaunchKernelGGL(blosc_gather_kernel, dim3((unsigned)jobs.size()), dim3(kThreads), 0, s,
-                         (const GatherJob*)(d8 + o_jobs));
-      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
-      if (timed) (void)hipEventRecord(ev[4], s);
-    }
-    if (rc == ZH_OK && !ring.d2h(dst + *pos, d8 + o_compact, (size_t)cpos)) rc = ZH_EHIP;
+  double gather_ms = 0;
+  rc = finish_slab(s, ring, mem, marks, 3, rc, L, dst, pos, &gather_ms);
+  if (rc == ZH_OK) {
+    part_ms[kMatch] += marks.ms(0, 1);
+    part_ms[kCoder] += marks.ms(1, 2);
+    part_ms[kGather] += gather_ms;
   }
-  if (hipStreamSynchronize(s) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
-  if (rc == ZH_OK && timed && !jobs.empty()) {
-    float a = 0, b = 0, c = 0;
-    if (hipEventElapsedTime(&a, ev[0], ev[1]) != hipSuccess) a = 0;
-    if (hipEventElapsedTime(&b, ev[1], ev[2]) != hipSuccess) b = 0;
-    if (hipEventElapsedTime(&c, ev[3], ev[4]) != hipSuccess) c = 0;
-    part_ms[kMatch] += (double)a;
-    part_ms[kCoder] += (double)b;
-    part_ms[kGather] += (double)c;
-  }
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  zh::ctx_release(ctx, dmem, got);
-  if (rc == ZH_OK) *pos += cpos;
   return rc;
 }
 
@@ -725,22 +695,17 @@ int crc_frames(zh_ctx* ctx, hipStream_t s, Ring& ring, const zh_gzip_enc_frame* 
     }
     uint8_t* d8 = (uint8_t*)dmem;
     if (!ring.h2d(d8, (const uint8_t*)cj.data(), cj.size() * sizeof(CrcJob))) rc = ZH_EHIP;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (auto& e : ev) (void)hipEventCreate(&e);
+    Marks marks(s, 2);
     if (rc == ZH_OK) {
-      if (ev[0]) (void)hipEventRecord(ev[0], s);
+      marks.mark(0);
       hipLaunchKernelGGL(gzip_crc32_kernel, dim3((unsigned)cj.size()), dim3(kThreads), 0, s,
                          (const CrcJob*)d8, zh_gz::xpow8(kPiece), (uint32_t*)(d8 + o_out));
       if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
-      if (ev[1]) (void)hipEventRecord(ev[1], s);
+      marks.mark(1);
     }
     if (rc == ZH_OK && !ring.d2h((uint8_t*)raw.data(), d8 + o_out, cj.size() * 4)) rc = ZH_EHIP;
     if (hipStreamSynchronize(s) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
-    float ms = 0;
-    if (rc == ZH_OK && ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-      *kernel_ms += (double)ms;
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
+    if (rc == ZH_OK) *kernel_ms += marks.ms(0, 1);
     zh::ctx_release(ctx, dmem, got);
     if (rc != ZH_OK) return rc;
   }
@@ -785,12 +750,12 @@ int zh::gzip_crc_launch(hipStream_t s, const void* d_jobs, uint32_t n, uint32_t*
 int zh::gzip_segments_launch(hipStream_t s, const void* d_rows, uint32_t n, bool dynamic,
                              uint8_t* d_scratch, uint16_t* d_seqs, uint32_t* d_info,
                              uint32_t* d_csize) {
-  static_assert(sizeof(::GBlock) == 32, "the layout zh_ctx.h describes");
+  static_assert(sizeof(::EncRow) == 32, "the layout zh_ctx.h describes");
   if (n == 0) return ZH_OK;
   zh_gz::Params P;
   P.dynamic = dynamic;
-  launch_match(P.B, s, (const ::GBlock*)d_rows, n, d_seqs, d_info);
-  launch_deflate(P, s, (const ::GBlock*)d_rows, n, d_scratch, d_seqs, d_info, d_csize);
+  launch_match(P.B, s, (const ::EncRow*)d_rows, n, d_seqs, d_info);
+  launch_deflate(P, s, (const ::EncRow*)d_rows, n, d_scratch, d_seqs, d_info, d_csize);
   return hipGetLastError() == hipSuccess ? ZH_OK : ZH_EHIP;
 }
 
@@ -839,9 +804,7 @@ int zh_gzip_encode_batch(zh_ctx* ctx, zh_gzip_enc_frame* frames, int64_t n,
     rc = crc_frames(ctx, s, ring, frames, n, crcs.data(), &part[kCrc]);
   }
   for (int64_t f0 = 0; f0 < n && rc == ZH_OK;) {
-    int64_t f1 = f0, raw = 0;
-    do raw += frames[f1++].nbytes;
-    while (f1 < n && raw + frames[f1].nbytes <= kSlabBytes);
+    const int64_t f1 = slab_end(frames, f0, n);
     rc = encode_slab(ctx, s, ring, crcs.data(), frames, f0, f1, P, (uint8_t*)dst, &pos, part);
     f0 = f1;
   }

@@ -25,6 +25,8 @@
 //           then the bytes, from the scratch (compressed blocks), from the raw source (raw
 //           blocks), from the uploaded frame headers or from the hash table (checksums);
 //   D2H     the compact buffer through the context's page-locked out ring into host memory.
+// encode_slab keeps the planning and the layout, which are this format; the slab's memory, marks,
+// cutting and tail (caps, upload, gather, download, synchronise) are the driver of zh_enc_device.h.
 // Slabs of at most kSlabBytes of raw input bound the device memory: per slab the scratch (the raw
 // size), the records (6 bytes per 4 raw bytes: 1.5 x), the compact frames (the raw size and the
 // headers) and the small tables.
@@ -43,22 +45,20 @@
 
 namespace {
 
-constexpr int64_t kSlabBytes = (int64_t)128 << 20;
-
 struct HashJob {
   uint64_t src, n;
 };
 
 template <uint32_t CAP, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void zstd_match_kernel(
-    const ZBlock* __restrict__ blocks, uint32_t nblocks, uint8_t* __restrict__ scratch,
+    const EncRow* __restrict__ blocks, uint32_t nblocks, uint8_t* __restrict__ scratch,
     uint16_t* __restrict__ seqs, uint32_t* __restrict__ info) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[WAVES][CAP];
   __shared__ uint32_t tables[WAVES][zh_lz::kHashSize];
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t k = blockIdx.x * WAVES + wave;
   if (k >= nblocks) return;  // the whole wave: the kernel has no barrier
-  const ZBlock b = blocks[k];
+  const EncRow b = blocks[k];
   if (b.size > CAP) return;  // never: the host picks CAP from the block size
   const uint8_t* __restrict__ src = (const uint8_t*)b.src;
   uint8_t* blk = lds[wave];
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(kThreads) void zstd_xxh64_kernel(const HashJob* __r
 
 std::atomic<double> g_last_zenc_ms{-1.0};
 
-void launch_match(uint32_t B, hipStream_t s, const ZBlock* blocks, uint32_t nblocks,
+void launch_match(uint32_t B, hipStream_t s, const EncRow* blocks, uint32_t nblocks,
                   uint8_t* scratch, uint16_t* seqs, uint32_t* info) {
   if (B <= (16u << 10)) {
     hipLaunchKernelGGL((zstd_match_kernel<(16u << 10), 4>), dim3((nblocks + 3) / 4), dim3(256), 0,
@@ -214,7 +214,7 @@ struct FramePlan {
 
 struct DevEmit {
   std::vector<GatherJob>* jobs;
-  const ZBlock* blocks;  // of this frame
+  const EncRow* blocks;  // of this frame
   uint64_t src, scratch, dst;
   void raw(uint32_t h, size_t off, uint32_t len) {
     jobs->push_back({src + off, dst, len, h, 3, 0});
@@ -232,15 +232,16 @@ int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, const zh_ze::Tables* dta
                 const zh_ze::Params& P, uint8_t* dst, int64_t* pos, double* kernel_ms) {
   const int64_t nf = f1 - f0;
   std::vector<FramePlan> plan((size_t)nf);
-  std::vector<ZBlock> blocks;
-  int64_t scratch_total = 0, seq_total = 0, compact_cap = 0, njobs_cap = 0;
+  std::vector<EncRow> blocks;
+  SlabLayout L;
+  int64_t scratch_total = 0, seq_total = 0;
   for (int64_t i = f0; i < f1; i++) {
     FramePlan& fp = plan[(size_t)(i - f0)];
     const size_t n = (size_t)frames[i].nbytes;
     fp.first_block = (int64_t)blocks.size();
     fp.nblocks = (int64_t)zh_ze::block_count(n, P.B);
     for (int64_t k = 0; k < fp.nblocks; k++) {
-      ZBlock b;
+      EncRow b;
       b.size = zh_ze::block_size(n, P.B, (size_t)k);
       b.src = (uint64_t)(uintptr_t)frames[i].src + (uint64_t)k * P.B;
       b.out = (uint64_t)scratch_total;
@@ -250,64 +251,53 @@ int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, const zh_ze::Tables* dta
       scratch_total += up(b.size, 16);
       seq_total += up(3 * (int64_t)(b.size / 4) + 3, 8);
     }
-    compact_cap += up((int64_t)zh_ze::raw_frame_size(n, P.checksum), 16);
-    njobs_cap += 4 + fp.nblocks + (int64_t)(n / zh_ze::kRawBlock);
+    L.compact_cap += up((int64_t)zh_ze::raw_frame_size(n, P.checksum), 16);
+    L.njobs_cap += 4 + fp.nblocks + (int64_t)(n / zh_ze::kRawBlock);
   }
-  if (blocks.size() > (size_t)zh::kIntMax || njobs_cap > zh::kIntMax) return ZH_EINVAL;
+  if (blocks.size() > (size_t)zh::kIntMax || L.njobs_cap > zh::kIntMax) return ZH_EINVAL;
   const size_t nb = blocks.size();
+  L.meta_cap = nf * 16;
 
   // device memory: [blocks | info | csize | jobs | meta | seqs | scratch | compact]
-  const size_t o_blocks = 0;
-  const size_t o_info = o_blocks + (size_t)up((int64_t)(nb * sizeof(ZBlock)), 256);
-  const size_t o_cs = o_info + (size_t)up((int64_t)nb * 8, 256);
-  const size_t o_jobs = o_cs + (size_t)up((int64_t)nb * 4, 256);
-  const size_t o_meta = o_jobs + (size_t)up(njobs_cap * (int64_t)sizeof(GatherJob), 256);
-  const size_t o_seq = o_meta + (size_t)up(nf * 16, 256);
-  const size_t o_scratch = o_seq + (size_t)up(seq_total * 2, 256);
-  const size_t o_compact = o_scratch + (size_t)up(scratch_total, 256);
-  const size_t need = o_compact + (size_t)compact_cap + 256;
-  void* dmem = nullptr;
-  size_t got = 0;
-  if (zh::ctx_alloc(ctx, need, &dmem, &got) != hipSuccess) {
-    (void)hipGetLastError();
-    return ZH_ENOMEM;
-  }
-  uint8_t* d8 = (uint8_t*)dmem;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (auto& e : ev) (void)hipEventCreate(&e);
-  const bool timed = ev[0] && ev[1] && ev[2] && ev[3];
-  int rc = ZH_OK;
+  SlabMem mem;
+  const size_t o_blocks = mem.add((int64_t)(nb * sizeof(EncRow)));
+  const size_t o_info = mem.add((int64_t)nb * 8);
+  const size_t o_cs = mem.add((int64_t)nb * 4);
+  L.o_jobs = mem.add(L.njobs_cap * (int64_t)sizeof(GatherJob));
+  L.o_meta = mem.add(L.meta_cap);
+  const size_t o_seq = mem.add(seq_total * 2);
+  const size_t o_scratch = mem.add(scratch_total);
+  L.o_compact = mem.add(L.compact_cap);
+  int rc = mem.alloc(ctx);
+  if (rc != ZH_OK) return rc;
+  Marks marks(s, 4);
   std::vector<uint32_t> cs(nb, 0);
-  if (nb && !ring.h2d(d8 + o_blocks, (const uint8_t*)blocks.data(), nb * sizeof(ZBlock)))
+  if (nb && !ring.h2d(mem.at(o_blocks), (const uint8_t*)blocks.data(), nb * sizeof(EncRow)))
     rc = ZH_EHIP;
   if (rc == ZH_OK) {
-    if (timed) (void)hipEventRecord(ev[0], s);
+    marks.mark(0);
     if (nb) {
-      launch_match(P.B, s, (const ZBlock*)(d8 + o_blocks), (uint32_t)nb, d8 + o_scratch,
-                   (uint16_t*)(d8 + o_seq), (uint32_t*)(d8 + o_info));
+      launch_match(P.B, s, (const EncRow*)mem.at(o_blocks), (uint32_t)nb, mem.at(o_scratch),
+                   (uint16_t*)mem.at(o_seq), (uint32_t*)mem.at(o_info));
       hipLaunchKernelGGL(zstd_fse_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, s,
-                         (const ZBlock*)(d8 + o_blocks), (uint32_t)nb, dtab, d8 + o_scratch,
-                         (const uint16_t*)(d8 + o_seq), (const uint32_t*)(d8 + o_info),
-                         (uint32_t*)(d8 + o_cs));
+                         (const EncRow*)mem.at(o_blocks), (uint32_t)nb, dtab, mem.at(o_scratch),
+                         (const uint16_t*)mem.at(o_seq), (const uint32_t*)mem.at(o_info),
+                         (uint32_t*)mem.at(o_cs));
     }
     if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
-    if (timed) (void)hipEventRecord(ev[1], s);
+    marks.mark(1);
   }
-  if (rc == ZH_OK && nb && !ring.d2h((uint8_t*)cs.data(), d8 + o_cs, nb * 4)) rc = ZH_EHIP;
+  if (rc == ZH_OK && nb && !ring.d2h((uint8_t*)cs.data(), mem.at(o_cs), nb * 4)) rc = ZH_EHIP;
   // the table lays out device copies: nothing in it may pass its block's raw size
   for (size_t k = 0; k < nb && rc == ZH_OK; k++)
     if (cs[k] == 0 || cs[k] > blocks[k].size) rc = ZH_EHIP;
 
   // layout: the frames side by side in the compact buffer, each 16-byte aligned
-  std::vector<GatherJob> jobs;
-  std::vector<uint8_t> meta;
-  int64_t cpos = 0;
   if (rc == ZH_OK) {
-    meta.resize((size_t)nf * 16, 0);
-    jobs.reserve((size_t)njobs_cap);
-    const uint64_t d_meta = (uint64_t)(uintptr_t)(d8 + o_meta);
-    const uint64_t d_scratch = (uint64_t)(uintptr_t)(d8 + o_scratch);
-    const uint64_t d_compact = (uint64_t)(uintptr_t)(d8 + o_compact);
+    L.meta.resize((size_t)nf * 16, 0);
+    L.jobs.reserve((size_t)L.njobs_cap);
+    const uint64_t d_meta = mem.addr(L.o_meta), d_scratch = mem.addr(o_scratch);
+    const uint64_t d_compact = mem.addr(L.o_compact);
     const uint64_t d_hash = (uint64_t)(uintptr_t)d_hashes;
     for (int64_t i = f0; i < f1; i++) {
       const FramePlan& fp = plan[(size_t)(i - f0)];
@@ -316,48 +306,26 @@ int encode_slab(zh_ctx* ctx, hipStream_t s, Ring& ring, const zh_ze::Tables* dta
       const uint32_t* fcs = fp.nblocks ? cs.data() + fp.first_block : nullptr;
       const size_t total = zh_ze::frame_size(n, P.B, fcs, P.checksum, &all_raw);
       const size_t m0 = (size_t)(i - f0) * 16;
-      zh_ze::put_frame_header(meta.data() + m0, n, P.checksum);
-      const uint64_t fbase = d_compact + (uint64_t)cpos;
-      jobs.push_back({d_meta + m0, fbase, (uint32_t)zh_ze::kFrameHeader, 0, 0, 0});
-      DevEmit e{&jobs, blocks.data() + fp.first_block, (uint64_t)(uintptr_t)frames[i].src,
+      zh_ze::put_frame_header(L.meta.data() + m0, n, P.checksum);
+      const uint64_t fbase = d_compact + (uint64_t)L.cpos;
+      L.jobs.push_back({d_meta + m0, fbase, (uint32_t)zh_ze::kFrameHeader, 0, 0, 0});
+      DevEmit e{&L.jobs, blocks.data() + fp.first_block, (uint64_t)(uintptr_t)frames[i].src,
                 d_scratch, fbase + zh_ze::kFrameHeader};
       zh_ze::walk_blocks(n, P.B, cs.data() + fp.first_block, all_raw, e);
       if (P.checksum) {
-        jobs.push_back({d_hash + 8 * (uint64_t)i, e.dst, 4, 0, 0, 0});
+        L.jobs.push_back({d_hash + 8 * (uint64_t)i, e.dst, 4, 0, 0, 0});
         e.dst += 4;
       }
       if (e.dst - fbase != total) rc = ZH_EHIP;  // layout and size disagree
-      frames[i].dst_off = *pos + cpos;
+      frames[i].dst_off = *pos + L.cpos;
       frames[i].cbytes = (int64_t)total;
       frames[i].status = ZH_OK;
-      cpos += up((int64_t)total, 16);
+      L.cpos += up((int64_t)total, 16);
     }
-    if ((int64_t)jobs.size() > njobs_cap || cpos > compact_cap) rc = ZH_EHIP;  // the allocation
   }
-  if (rc == ZH_OK && !jobs.empty()) {
-    if (!ring.h2d(d8 + o_jobs, (const uint8_t*)jobs.data(), jobs.size() * sizeof(GatherJob)) ||
-        !ring.h2d(d8 + o_meta, meta.data(), meta.size()))
-      rc = ZH_EHIP;
-    if (rc == ZH_OK) {
-      if (timed) (void)hipEventRecord(ev[2], s);
-      hipLaunchKernelGGL(blosc_gather_kernel, dim3((unsigned)jobs.size()), dim3(kThreads), 0, s,
-                         (const GatherJob*)(d8 + o_jobs));
-      if (hipGetLastError() != hipSuccess) rc = ZH_EHIP;
-      if (timed) (void)hipEventRecord(ev[3], s);
-    }
-    if (rc == ZH_OK && !ring.d2h(dst + *pos, d8 + o_compact, (size_t)cpos)) rc = ZH_EHIP;
-  }
-  if (hipStreamSynchronize(s) != hipSuccess) rc = rc == ZH_OK ? ZH_EHIP : rc;
-  if (rc == ZH_OK && timed && !jobs.empty()) {
-    float a = 0, b = 0;
-    if (hipEventElapsedTime(&a, ev[0], ev[1]) != hipSuccess) a = 0;
-    if (hipEventElapsedTime(&b, ev[2], ev[3]) != hipSuccess) b = 0;
-    *kernel_ms += (double)a + (double)b;
-  }
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  zh::ctx_release(ctx, dmem, got);
-  if (rc == ZH_OK) *pos += cpos;
+  double gather_ms = 0;
+  rc = finish_slab(s, ring, mem, marks, 2, rc, L, dst, pos, &gather_ms);
+  if (rc == ZH_OK) *kernel_ms += marks.ms(0, 1) + gather_ms;
   return rc;
 }
 
@@ -368,19 +336,14 @@ int hash_frames(hipStream_t s, Ring& ring, const zh_zstd_enc_frame* frames, int6
   for (int64_t i = 0; i < n; i++)
     hj[(size_t)i] = {(uint64_t)(uintptr_t)frames[i].src, (uint64_t)frames[i].nbytes};
   if (!ring.h2d(d_jobs, (const uint8_t*)hj.data(), hj.size() * sizeof(HashJob))) return ZH_EHIP;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  for (auto& e : ev) (void)hipEventCreate(&e);
-  if (ev[0]) (void)hipEventRecord(ev[0], s);
+  Marks marks(s, 2);
+  marks.mark(0);
   hipLaunchKernelGGL(zstd_xxh64_kernel, dim3((unsigned)((n + kWaves - 1) / kWaves)),
                      dim3(kThreads), 0, s, (const HashJob*)d_jobs, (uint32_t)n, d_hashes);
   int rc = hipGetLastError() == hipSuccess ? ZH_OK : ZH_EHIP;
-  if (ev[1]) (void)hipEventRecord(ev[1], s);
+  marks.mark(1);
   if (hipStreamSynchronize(s) != hipSuccess) rc = ZH_EHIP;
-  float ms = 0;
-  if (rc == ZH_OK && ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-    *kernel_ms += (double)ms;
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
+  if (rc == ZH_OK) *kernel_ms += marks.ms(0, 1);
   return rc;
 }
 
@@ -456,9 +419,7 @@ int zh_zstd_encode_batch(zh_ctx* ctx, zh_zstd_enc_frame* frames, int64_t n,
   }
   const uint64_t* d_hashes = hmem ? (const uint64_t*)((uint8_t*)hmem + o_hashes) : nullptr;
   for (int64_t f0 = 0; f0 < n && rc == ZH_OK;) {
-    int64_t f1 = f0, raw = 0;
-    do raw += frames[f1++].nbytes;
-    while (f1 < n && raw + frames[f1].nbytes <= kSlabBytes);
+    const int64_t f1 = slab_end(frames, f0, n);
     rc = encode_slab(ctx, s, ring, dtab, d_hashes, frames, f0, f1, P, (uint8_t*)dst, &pos, &ms);
     f0 = f1;
   }
